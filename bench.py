@@ -2,8 +2,25 @@
 """Benchmark of the SRC -> 6-biquad EQ -> FFT chain on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c3|c5]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: it builds the
+chain, warms up, times the K steps, writes the outputs if `--dump-outputs` is
+given and prints the result line (the contract fields, `config` and
+`chain_roofline`).  Everything else described below -- the traced pass behind
+`roofline`, `kernels_ms` and the per-rank kernel means, the CPU baseline, the
+other configs, `host_inclusive`, `app_rerun`, `eq_alone`, `ratio_sweep`, the
+ceilings and `fft_2_28` -- takes runs of its own and is measured only with
+`--full`.
+
+`--dump-outputs DIR` writes what the last timed step left in the chain's output
+buffers, the (y, z, mag) a caller of Chain.run receives, as DIR/y.npy, DIR/z.npy
+and DIR/mag.npy (float32): the same DUMP_ROWS seeded channel rows of each, in
+ascending channel order (37 MB at config 4).  The input is seeded, so two
+builds run with the same arguments can be compared output for output.  Ranks
+above 0 of an N > 1 run write <name>.rank<r>.npy.
 
 `--gpus N` without a launcher (WORLD_SIZE unset) starts the N ranks itself: N
 fresh child processes with RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set, created
@@ -16,9 +33,9 @@ fs' = 72 kHz, and a 4096-point Hann-windowed FFT magnitude of the centre
 segment of z; the 32768 channels are sharded over the N ranks (32768/N each,
 strong scaling), so every N runs the same job.  `--config c3` is configs[2]
 (4096 channels), `--config c5` configs[4] (8192 channels, 44.1 -> 48 kHz,
-L/M = 160/147, K = 1023), both sharded the same way.  At N = 1 the default
-run also times config 3 (4096 channels, one GPU) and reports it under
-"config3".
+L/M = 160/147, K = 1023), both sharded the same way.  At N = 1 a `--full`
+run also times the other two configs on one GPU and reports them under
+"config3" / "config4" / "config5".
 
 Input is synthetic uniform(-1, 1) float32 generated on the device (the
 reference's example WAVs are missing), resident in HBM before the timed
@@ -27,8 +44,8 @@ shard with no collective: the only cross-rank calls are the timing barrier and
 the max-over-ranks of the elapsed time, over gloo (CPU; RCCL is never
 initialised).
 
-Rank 0 prints one JSON line.  Besides the contract fields it carries
-`roofline` (dominant kernel: algorithmic bytes per launch / its mean duration
+Rank 0 prints one JSON line.  With `--full` it carries, besides the contract
+fields, `roofline` (dominant kernel: algorithmic bytes per launch / its mean duration
 from HIP events the library records around every launch on the launching
 stream, against the 8 TB/s spec and against a float4 copy measured in the same
 process, and the PMC-measured HBM bytes of that kernel when profiles hold them
@@ -303,9 +320,34 @@ def load_traffic(wl_name, channels):
     return ent.get("per_launch", {}), ent.get("source")
 
 
-def measure(wl, B, steps, warmup, rank, world, dist, eager, device, same_node=True):
+DUMP_ROWS = 64             # channel rows of each output that --dump-outputs keeps
+DUMP_BYTES = 64 << 20      # ... fewer where that many rows would exceed this in all
+
+
+def dump_outputs(dirname, outputs, rank=0):
+    """Writes `outputs` (name -> [B, n] device tensor, None skipped) as
+    <dirname>/<name>.npy in float32: the same rows of each, a seeded sample of
+    the B channels in ascending order (all of them where B <= DUMP_ROWS)."""
+    import numpy as np
+    import torch
+    outputs = {k: t for k, t in outputs.items() if t is not None}
+    B = next(iter(outputs.values())).shape[0]
+    row_bytes = 4 * sum(t.shape[1] for t in outputs.values())
+    rows = max(1, min(B, DUMP_ROWS, DUMP_BYTES // row_bytes))
+    idx = np.sort(np.random.default_rng(2024).choice(B, rows, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    suffix = "" if rank == 0 else f".rank{rank}"
+    for name, t in outputs.items():
+        sel = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"),
+                sel.to(torch.float32).cpu().numpy())
+
+
+def measure(wl, B, steps, warmup, rank, world, dist, eager, device, same_node=True,
+            trace=True, dump_dir=None):
     """Builds the chain for B channels of workload wl, times K steps (graph
-    replay unless eager) and a traced pass; returns the numbers."""
+    replay unless eager), writes the last step's outputs to dump_dir if given
+    and, with `trace`, runs a traced pass; returns the numbers."""
     import torch
 
     from dspcore import _lib
@@ -342,29 +384,35 @@ def measure(wl, B, steps, warmup, rank, world, dist, eager, device, same_node=Tr
     st = {}
     elapsed = timed_loop(step, steps, warmup, sync, dist, same_node=same_node, stats=st)
     chain.check()      # raises HandoffError if a tile hand-off wait gave up
+    if dump_dir:
+        # the chain's own output buffers: what the last timed step wrote
+        dump_outputs(dump_dir, {"y": chain.y, "z": chain.z, "mag": chain.mag}, rank)
 
-    # Traced pass: HIP events around every launch, on the kernels' stream.
-    _lib.trace_enable(True)
-    _lib.trace_read()
-    for _ in range(steps):
-        chain.run(x, check=False)
-    recs = _lib.trace_read()
-    _lib.trace_enable(False)
-    chain.check()
-    per = {}
-    for name, ms in recs:
-        per.setdefault(name, []).append(ms)
-    kernels = {k: round(sum(v) / len(v), 5) for k, v in per.items()}
-    dom = max(kernels, key=kernels.get)
+    kernels, dom = {}, None
+    if trace:
+        # Traced pass: HIP events around every launch, on the kernels' stream.
+        _lib.trace_enable(True)
+        _lib.trace_read()
+        for _ in range(steps):
+            chain.run(x, check=False)
+        recs = _lib.trace_read()
+        _lib.trace_enable(False)
+        chain.check()
+        per = {}
+        for name, ms in recs:
+            per.setdefault(name, []).append(ms)
+        kernels = {k: round(sum(v) / len(v), 5) for k, v in per.items()}
+        dom = max(kernels, key=kernels.get)
     res = dict(chain=chain, elapsed=elapsed, local=st["local"], launch=launch, kernels=kernels,
-               dom=dom, dom_bytes=kernel_bytes(chain, dom))
+               dom=dom, dom_bytes=kernel_bytes(chain, dom) if dom else 0)
     del x
     return res
 
 
-def measure_stub(wl, B, steps):
+def measure_stub(wl, B, steps, trace=True):
     """DSP_BENCH_DRYRUN=1: the shapes and bookkeeping of measure() without a
-    GPU (tests of the rank launcher and sharding; numbers are placeholders)."""
+    GPU (tests of the rank launcher and sharding; numbers are placeholders).
+    Nothing is computed, so --dump-outputs writes nothing."""
     from types import SimpleNamespace
 
     from dspcore import design
@@ -374,8 +422,12 @@ def measure_stub(wl, B, steps):
     chain = SimpleNamespace(B=B, n_out=src.n_out, tile_len=0, cfg=SimpleNamespace(n_in=wl["n_in"]),
                             spec=spec, algorithmic_bytes=lambda: per * B)
     ms = 1e-6 * B + 1e-3
-    return dict(chain=chain, elapsed=steps * ms * 1e-3, local=steps * ms * 1e-3, launch="dry-run",
-                kernels={"chain_tile": ms}, dom="chain_tile", dom_bytes=kernel_bytes(chain, "chain_tile"))
+    res = dict(chain=chain, elapsed=steps * ms * 1e-3, local=steps * ms * 1e-3, launch="dry-run",
+               kernels={}, dom=None, dom_bytes=0)
+    if trace:
+        res.update(kernels={"chain_tile": ms}, dom="chain_tile",
+                   dom_bytes=kernel_bytes(chain, "chain_tile"))
+    return res
 
 
 def extra_line(wl, r, steps):
@@ -740,13 +792,23 @@ def main(argv=None):
     ap.add_argument("--config", choices=sorted(WORKLOADS), default="c4")
     ap.add_argument("--channels", type=int, default=None,
                     help="total channels over all ranks (default: the config's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the traced pass "
+                         "(roofline, kernels_ms), the CPU baseline and, at N = 1, the other "
+                         "configs, host-inclusive rate, app rerun, EQ alone, ratio sweep, "
+                         "ceilings and the 2^28 FFT")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's y, z and mag (a seeded sample of "
+                         "channel rows, float32) as DIR/<name>.npy")
     ap.add_argument("--cpu-per-proc", type=int, default=None,
-                    help="CPU-baseline channels per process (0 = skip; default per config)")
+                    help="with --full: CPU-baseline channels per process (0 = skip; default "
+                         "per config)")
     ap.add_argument("--no-extras", "--no-config3", dest="no_extras", action="store_true",
-                    help="skip the config-3/config-5, host-inclusive and copy-ceiling "
-                         "measurements at N = 1")
+                    help="with --full: skip the config-3/config-5, host-inclusive and "
+                         "copy-ceiling measurements at N = 1")
     ap.add_argument("--no-sweep", action="store_true",
-                    help="skip the L/M ratio sweep (every app ratio at 4096 channels)")
+                    help="with --full: skip the L/M ratio sweep (every app ratio at 4096 "
+                         "channels)")
     ap.add_argument("--eager", action="store_true",
                     help="launch every step from Python instead of replaying a HIP graph")
     args = ap.parse_args(argv)
@@ -767,7 +829,7 @@ def main(argv=None):
     # CPU baseline first: no GPU context exists yet when the pool forks.
     cpu = None
     per_proc = wl["cpu_per_proc"] if args.cpu_per_proc is None else args.cpu_per_proc
-    if rank == 0 and world == 1 and per_proc > 0 and not dry:
+    if args.full and rank == 0 and world == 1 and per_proc > 0 and not dry:
         cpu = cpu_baseline(wl, usable_cores()[0], per_proc)
 
     import torch
@@ -793,7 +855,7 @@ def main(argv=None):
         dist.all_gather_object(hosts, socket.gethostname())
         same_node = len(set(hosts)) == 1
     if dry:
-        r = measure_stub(wl, B, args.steps)
+        r = measure_stub(wl, B, args.steps, trace=args.full)
         if dist is not None:
             dist.barrier()
         device = None
@@ -804,7 +866,7 @@ def main(argv=None):
         device = torch.device("cuda", dev_index)
         torch.cuda.set_device(device)
         r = measure(wl, B, args.steps, args.warmup, rank, world, dist, args.eager, device,
-                    same_node)
+                    same_node, trace=args.full, dump_dir=args.dump_outputs)
     chain, elapsed, kernels, dom = r["chain"], r["elapsed"], r["kernels"], r["dom"]
     if dist is not None and dry:
         t = torch.tensor([elapsed], dtype=torch.float64)
@@ -812,37 +874,40 @@ def main(argv=None):
         elapsed = float(t.item())
     per_rank = None
     if dist is not None:
-        # every rank's own timed region, dominant-kernel mean and shard: the
-        # N > 1 line shows the spread (a slow or throttled GPU, an imbalance)
-        mine = torch.tensor([r["local"] * 1e3 / args.steps, kernels[dom], float(B)],
-                            dtype=torch.float64)
+        # every rank's own timed region, dominant-kernel mean (--full: the
+        # traced pass) and shard: the N > 1 line shows the spread (a slow or
+        # throttled GPU, an imbalance)
+        mine = torch.tensor([r["local"] * 1e3 / args.steps, kernels[dom] if dom else 0.0,
+                             float(B)], dtype=torch.float64)
         allr = [torch.zeros(3, dtype=torch.float64) for _ in range(world)]
         dist.all_gather(allr, mine)
         ms_r = [float(t[0]) for t in allr]
         dom_r = [float(t[1]) for t in allr]
         per_rank = {
             "elapsed_ms_min": round(min(ms_r), 4), "elapsed_ms_max": round(max(ms_r), 4),
-            f"{dom}_ms_min": round(min(dom_r), 5), f"{dom}_ms_max": round(max(dom_r), 5),
+            **({f"{dom}_ms_min": round(min(dom_r), 5), f"{dom}_ms_max": round(max(dom_r), 5)}
+               if dom else {}),
             "channels": [int(t[2]) for t in allr],
             "elapsed_ms": [round(v, 4) for v in ms_r],
-            f"{dom}_ms": [round(v, 5) for v in dom_r],
+            **({f"{dom}_ms": [round(v, 5) for v in dom_r]} if dom else {}),
             "timing": ("max(end) - min(start), one node's monotonic clock" if same_node
                        else "max over ranks of each rank's elapsed (ranks on several nodes)"),
-            "note": "elapsed_ms: per step, each rank's own timed region; "
-                    f"{dom}_ms: its HIP-event mean",
+            "note": "elapsed_ms: per step, each rank's own timed region"
+                    + (f"; {dom}_ms: its HIP-event mean" if dom else ""),
         }
     ms_per_step = elapsed / args.steps * 1e3
     value = total * wl["n_in"] * args.steps / elapsed / 1e6
-    mean_ms = kernels[dom]
-    achieved = r["dom_bytes"] / (mean_ms * 1e-3) / 1e9
-    traffic_map, traffic_src = load_traffic(wl["name"], B)
-    traffic = traffic_map.get(dom)
-    valu = valu_work(chain, mean_ms) if dom == "chain_tile" else None
+    if args.full:
+        mean_ms = kernels[dom]
+        achieved = r["dom_bytes"] / (mean_ms * 1e-3) / 1e9
+        traffic_map, traffic_src = load_traffic(wl["name"], B)
+        traffic = traffic_map.get(dom)
+        valu = valu_work(chain, mean_ms) if dom == "chain_tile" else None
     chain_bytes = chain.algorithmic_bytes()
     chain_gbs = chain_bytes / (ms_per_step * 1e-3) / 1e9
     launch, n_out, dom_bytes = r["launch"], chain.n_out, r["dom_bytes"]
     extras = {}
-    if world == 1 and not args.no_extras and not dry:
+    if args.full and world == 1 and not args.no_extras and not dry:
         del chain, r
         torch.cuda.empty_cache()
         for key in ("c3", "c4", "c5"):
@@ -895,7 +960,17 @@ def main(argv=None):
                 "launch": launch,
                 "preheat_s": PREHEAT_S,
             },
-            "roofline": {
+            "chain_roofline": {
+                "achieved": round(chain_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(chain_gbs / HBM_PEAK_GBS, 4),
+                "frac_vs_copy_ceiling": round(chain_gbs / ceiling, 4) if ceiling else None,
+                "algorithmic_bytes_per_gpu_step": chain_bytes,
+            },
+            **({"per_rank": per_rank} if per_rank else {}),
+            "full": args.full,
+        }
+        if args.full:
+            out["roofline"] = {
                 "bound": "hbm", "kernel": dom, "achieved": round(achieved, 1),
                 "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                 "traffic": traffic,
@@ -911,25 +986,15 @@ def main(argv=None):
                 "algorithmic_bytes": dom_bytes,
                 "mean_ms": mean_ms,
                 "valu": valu,
-            },
-            "chain_roofline": {
-                "achieved": round(chain_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(chain_gbs / HBM_PEAK_GBS, 4),
-                "frac_vs_copy_ceiling": round(chain_gbs / ceiling, 4) if ceiling else None,
-                "algorithmic_bytes_per_gpu_step": chain_bytes,
-            },
-            "kernels_ms": kernels,
-            **({"per_rank": per_rank} if per_rank else {}),
-            **{k: extras.get(k) for k in ("config3", "config4", "config5") if k in extras},
-            "host_inclusive": extras.get("host_inclusive"),
-            "app_rerun": extras.get("app_rerun"),
-            "eq_alone": extras.get("eq_alone"),
-            **({"ratio_sweep": extras["ratio_sweep"]} if extras.get("ratio_sweep") else {}),
-            "copy_ceiling": extras.get("copy_ceiling"),
-            "mix_ceiling": extras.get("mix_ceiling"),
-            **({"fft_2_28": extras["fft_2_28"]} if extras.get("fft_2_28") else {}),
-            "cpu_baseline": cpu,
-        }
+            }
+            out["kernels_ms"] = kernels
+            out.update({k: extras[k] for k in ("config3", "config4", "config5") if k in extras})
+            for k in ("host_inclusive", "app_rerun", "eq_alone", "ratio_sweep", "copy_ceiling",
+                      "mix_ceiling", "fft_2_28"):
+                # ratio_sweep and fft_2_28 appear only when measured
+                if extras.get(k) or k not in ("ratio_sweep", "fft_2_28"):
+                    out[k] = extras.get(k)
+            out["cpu_baseline"] = cpu
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

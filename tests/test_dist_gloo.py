@@ -108,14 +108,15 @@ def test_bench_gpus_flag_launches_the_ranks_itself():
     """`python bench.py --gpus 2` with no launcher starts two ranks (fresh
     processes, gloo rendezvous on 127.0.0.1) that shard config 4's 32768
     channels (0, 16384) and (16384, 32768); rank 0 alone prints the line.
-    DSP_BENCH_DRYRUN stubs the GPU measurement (measure_stub)."""
+    DSP_BENCH_DRYRUN stubs the GPU measurement (measure_stub); --full, for the
+    per-rank kernel means and the cpu_baseline field."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
-                          "--steps", "3", "--warmup", "1"], capture_output=True, text=True,
-                         timeout=300, env=_bench_env(), cwd=root)
+                          "--steps", "3", "--warmup", "1", "--full"], capture_output=True,
+                         text=True, timeout=300, env=_bench_env(), cwd=root)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), res.stdout   # stdout: the JSON line only

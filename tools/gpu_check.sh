@@ -16,7 +16,7 @@ tail -1 "$OUT/smoke.log"
 for c in $CFGS; do
   [ "$c" = none ] && continue
   echo "== bench $c"
-  timeout -k 10 600 python bench.py --config $c > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || { tail -20 "$OUT/bench_$c.err"; exit 1; }
+  timeout -k 10 600 python bench.py --full --config $c > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || { tail -20 "$OUT/bench_$c.err"; exit 1; }
   cut -c1-400 "$OUT/bench_$c.json"
   python -c "import json,sys; d=json.load(open('$OUT/bench_$c.json')); print('value', d['value'], 'ms', d['ms_per_step'], 'kernels', d['kernels_ms'], 'frac', d['roofline']['frac'], 'chain', d['chain_roofline']['frac'], 'cfg3', (d.get('config3') or {}).get('ms_per_step'), (d.get('config3') or {}).get('kernels_ms'), 'cpu', (d.get('cpu_baseline') or {}).get('value'), (d.get('cpu_baseline') or {}).get('cores'))"
 done

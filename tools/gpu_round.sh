@@ -26,7 +26,7 @@ cp pmc_traffic.json "$OUT/pmc_traffic.json"
 for c in c4 c5; do
   echo "== bench $c"
   extra=""; [ $c = c5 ] && extra="--no-extras"
-  timeout -k 10 600 python bench.py --config $c $extra > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || { tail -20 "$OUT/bench_$c.err"; exit 1; }
+  timeout -k 10 600 python bench.py --full --config $c $extra > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || { tail -20 "$OUT/bench_$c.err"; exit 1; }
   cut -c1-300 "$OUT/bench_$c.json"
 done
 cd /tmp && export TMPDIR=/tmp
