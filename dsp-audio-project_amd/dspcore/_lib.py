@@ -37,7 +37,8 @@ DSP_LFILTER_NF_MAX = 4096
 _c_i32, _c_i64, _c_u64, _c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_size_t
 _vp, _dp = ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)
 
-# name -> (restype, argtypes); mirrors include/dspcore.h one to one.
+# name -> (restype, argtypes); mirrors include/dspcore.h one to one, then
+# include/dspcore_stream.h.  load() requires every one to be exported.
 _SIGNATURES = {
     "dsp_version": (ctypes.c_int, []),
     "dsp_last_error": (ctypes.c_char_p, []),
@@ -97,7 +98,18 @@ _SIGNATURES = {
     "dsp_wav_header_pcm16": (ctypes.c_int, [ctypes.c_char_p, _c_i32, _c_i32, _c_i64]),
     "dsp_trace_enable": (ctypes.c_int, [_c_i32]),
     "dsp_trace_read": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_float), _c_i32]),
+    # include/dspcore_stream.h
+    "dsp_stream_version": (ctypes.c_int, []),
+    "dsp_stream_cascade_f32": (ctypes.c_int, [
+        _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _dp, _c_i32, _c_i32, _vp, _vp, _c_i64, _vp]),
+    "dsp_stream_src_geometry": (ctypes.c_int, [
+        _c_i32, _c_i32, _c_i32, _c_i64, _c_i64, _c_i64, _c_i32, ctypes.POINTER(_c_i64),
+        ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64)]),
+    "dsp_stream_roll_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _c_i64, _vp]),
 }
+STREAM_HEADER_PATH = os.path.join(REPO_ROOT, "include", "dspcore_stream.h")
+DSP_STREAM_MAX_STAGES = 8
+DSP_STREAM_MAX_HIST = 4096
 DSP_TRACE_NAME = 32
 DSP_WAV_PCM = 1
 DSP_WAV_FLOAT = 3

@@ -84,6 +84,72 @@ def src_plan(n_in: int, fs: int, M: int, L: int, num_taps: int | None = None) ->
     return SrcPlan(L, M, K, h, c, n_in, n_out, int(fs * L / M))
 
 
+STREAM_MAX_HIST = 4096   # include/dspcore_stream.h DSP_STREAM_MAX_HIST
+
+
+@dataclass(frozen=True)
+class StreamSrcPlan:
+    """The polyphase SRC as a stream (include/dspcore_stream.h): the taps of
+    src_plan, centred at c = (K - 1) / 2 whatever the signal's length, and the
+    dsp_src_polyphase_f32 call that serves each block.  The staging row of a
+    block is [hist samples of history | block]; the history is zeros at the
+    start of the stream."""
+    L: int
+    M: int
+    K: int                 # odd tap count
+    taps: np.ndarray       # float64 L*h, length K (src_plan's)
+    c: int                 # (K - 1) // 2
+    hist: int              # ceil(K / L) - 1 input samples carried between blocks
+    fs_out: int
+
+    def ready(self, consumed: int) -> int:
+        """Outputs computable from `consumed` inputs: every m with
+        (m M + c) div L < consumed."""
+        return max(0, -(-(int(consumed) * self.L - self.c) // self.M))
+
+    def _call(self, consumed: int, produced: int, upto: int) -> tuple[int, int, int]:
+        consumed, produced = int(consumed), int(produced)
+        if consumed < 0 or produced != self.ready(consumed):
+            raise ValueError(f"produced={produced} is not what consumed={consumed} inputs make "
+                             f"computable ({self.ready(max(consumed, 0))})")
+        c_offset = produced * self.M + self.c - (consumed - self.hist) * self.L
+        return self.hist, c_offset, upto - produced
+
+    def block(self, consumed: int, produced: int, n_block: int) -> tuple[int, int, int]:
+        """(hist, c_offset, n_out) of the SRC call for a block of n_block inputs
+        after `consumed` inputs and `produced` outputs: n_in = hist + n_block on
+        the staging row.  n_out may be 0 (nothing to launch)."""
+        if n_block < 0:
+            raise ValueError("n_block must be >= 0")
+        return self._call(consumed, produced, self.ready(int(consumed) + int(n_block)))
+
+    def flush(self, consumed: int, produced: int) -> tuple[int, int, int]:
+        """(hist, c_offset, n_out) of the call that ends the stream: n_in =
+        hist, the outputs up to ceil(consumed L / M) whose windows reach past
+        the last input.  With consumed * L >= K the concatenated blocks are the
+        one-shot src_plan call's output; a shorter stream still gets
+        ceil(consumed L / M) outputs centred at c, where the one-shot call
+        centres at (consumed L - 1) // 2 and returns ceil(K / M)."""
+        return self._call(consumed, produced, -(-int(consumed) * self.L // self.M))
+
+
+def stream_src_plan(fs: int, M: int, L: int, num_taps: int | None = None) -> StreamSrcPlan:
+    """Plans conversion_tasa_muestreo(x, fs, M, L) as a stream: src_plan's
+    filter (wc = 1/max(L, M), K from `num_taps` or 40 max(L, M) + 1, h *= L,
+    dsp_core.py:155-162), no signal length."""
+    L, M = int(L), int(M)
+    if L < 1 or M < 1:
+        raise ValueError(f"L and M must be >= 1 (got L={L}, M={M})")
+    taps_req = default_num_taps(L, M) if num_taps is None else int(num_taps)
+    h = sinc_lowpass(1.0 / max(L, M), taps_req)
+    h *= L
+    K = h.size
+    hist = -(-K // L) - 1
+    if hist > STREAM_MAX_HIST:
+        raise RuntimeError(f"SRC history ceil(K/L)-1={hist} exceeds {STREAM_MAX_HIST} samples")
+    return StreamSrcPlan(L, M, K, h, (K - 1) // 2, hist, int(fs * L / M))
+
+
 # The library's flush rule (csrc/common.h, kTapFlushRel): taps at or below
 # this fraction of the largest (float32 arithmetic) are zero in its finite sums.
 TAP_FLUSH_REL = np.float32(1e-12)

@@ -218,6 +218,49 @@ def biquad_cascade(x: torch.Tensor, sos: np.ndarray, clip: bool,
     return out
 
 
+def biquad_cascade_state(x: torch.Tensor, sos: np.ndarray, clip: bool,
+                         zi: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                         zf: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """(z, zf): z = clip(cascade(x)) per row started from the state zi, and
+    the state after the row's last sample (dsp_stream_cascade_f32,
+    include/dspcore_stream.h).  Feeding a block's zf to the next block as zi
+    continues the filter: the concatenated z is the one-shot biquad_cascade of
+    the concatenated rows, to float64 rounding.
+
+    zi, zf: float64 CUDA [B, >= 2S], the kernels' direct-form-II delay lines
+    (w1_0, w2_0, w1_1, ...) of design.state_space -- not scipy's `zi`, and valid
+    only for the `sos` that produced them.  zi=None starts from rest; zf=None
+    allocates [B, 2S]; zi may be zf (in place), out may be x.  At most 8
+    stages.  The clip applies to z only, never to the state."""
+    x = _rows(x, "x")
+    if x.dtype != torch.float32:
+        x = x.float()
+    sos = np.ascontiguousarray(sos, dtype=np.float64).reshape(-1, 5)
+    B, n = x.shape
+    S = sos.shape[0]
+    if out is None:
+        out = torch.empty_like(x)
+    if zf is None:
+        zf = torch.zeros((B, max(2 * S, 1)), dtype=torch.float64, device=x.device)
+    for name, t in (("zi", zi), ("zf", zf)):
+        if t is None:
+            continue
+        if (not t.is_cuda or t.dtype != torch.float64 or t.dim() != 2 or t.shape[0] != B
+                or t.shape[1] < 2 * S or t.stride(1) != 1):
+            raise ValueError(f"{name} must be a float64 CUDA [B={B}, >= {2 * S}] tensor with "
+                             f"contiguous rows")
+    ld_state = ld(zf)
+    if zi is not None and ld(zi) != ld_state:
+        raise ValueError("zi and zf must share one row pitch")
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        rc = lib.dsp_stream_cascade_f32(
+            _ptr(x), _ptr(out), B, n, ld(x), ld(out), _lib.sos_pointer(sos), S,
+            int(bool(clip)), _ptr(zi), _ptr(zf), ld_state, _stream(x.device))
+    _lib.check(rc, "dsp_stream_cascade_f32")
+    return out, zf
+
+
 _ONE_TAP = SrcPlan(1, 1, 1, np.ones(1), 0, 0, 0, 0)
 
 

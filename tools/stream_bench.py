@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""Streaming throughput: StreamChain pushes against the one-shot Chain.
+
+Ratio 3/2 (48 -> 72 kHz), config-3 gains, blocks of 480 and 4800 input
+samples, 64 and 4096 channels.  Every (block, channels) step runs in a child
+process of its own under a time limit: 200 pushes after a warm-up, timed on
+the host (launch overhead included, one synchronisation at the end) and with
+HIP events; beside it the one-shot Chain on the same channels and the same
+total number of samples (200 blocks in one row per channel).  A step that
+fails or runs out of time ends the run: nothing more is started.
+
+    python tools/stream_bench.py [--out profiles/stream_bench.json]
+
+Writes one JSON document: the device name and one record per step with ms per
+push and input samples/s of the stream, and samples/s of the one-shot chain.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (os.path.join(ROOT, "dsp-audio-project_amd"), ROOT):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+FS, L, M = 48000, 3, 2
+BLOCKS = (480, 4800)
+BATCHES = (64, 4096)
+PUSHES = 200
+WARMUP = 20
+STEP_TIMEOUT_S = 240
+
+
+def one_step(block: int, batch: int) -> dict:
+    import torch
+
+    from dspcore.chain import Chain, ChainConfig
+    from dspcore.stream import StreamChain
+    from oracle import dsp_ref_cpu as orc
+
+    dev = torch.device("cuda", 0)
+    gains = orc.CONFIG3_GAINS
+    gen = torch.Generator(device=dev).manual_seed(5)
+    xb = torch.rand((batch, block), device=dev, generator=gen) * 2 - 1
+    sc = StreamChain(FS, L, M, None, gains, batch, block, dev)
+    for _ in range(WARMUP):
+        sc.push(xb)
+    torch.cuda.synchronize(dev)
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    start.record()
+    for _ in range(PUSHES):
+        sc.push(xb)
+    stop.record()
+    torch.cuda.synchronize(dev)
+    wall_ms = (time.perf_counter() - t0) * 1e3
+    gpu_ms = start.elapsed_time(stop)
+    del sc
+    # one-shot chain: the same channels, 200 blocks in one row each
+    n_in = block * PUSHES
+    x = xb.repeat(1, PUSHES)
+    ch = Chain(ChainConfig(n_in, FS, L, M, None, gains), batch, dev)
+    ch.run(x)
+    torch.cuda.synchronize(dev)
+    reps = 3
+    start.record()
+    for _ in range(reps):
+        ch.run(x, check=False)
+    stop.record()
+    torch.cuda.synchronize(dev)
+    ch.check()
+    chain_ms = start.elapsed_time(stop) / reps
+    samples = batch * block * PUSHES
+    return {
+        "block": block, "batch": batch, "pushes": PUSHES,
+        "stream_ms_per_push": wall_ms / PUSHES,
+        "stream_gpu_ms_per_push": gpu_ms / PUSHES,
+        "stream_samples_per_s": samples / (wall_ms * 1e-3),
+        "chain_ms": chain_ms,
+        "chain_samples_per_s": samples / (chain_ms * 1e-3),
+        "device": torch.cuda.get_device_name(dev),
+    }
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_bench.json"))
+    ap.add_argument("--one", nargs=2, type=int, metavar=("BLOCK", "BATCH"),
+                    help="run one step in this process and print its record")
+    args = ap.parse_args()
+    if args.one:
+        print(json.dumps(one_step(*args.one)))
+        return 0
+    steps = []
+    for batch in BATCHES:
+        for block in BLOCKS:
+            try:
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", str(block),
+                                    str(batch)], capture_output=True, text=True,
+                                   timeout=STEP_TIMEOUT_S)
+            except subprocess.TimeoutExpired:
+                print(f"step block={block} batch={batch} ran out of time; stopping",
+                      file=sys.stderr)
+                return 1
+            if r.returncode != 0:
+                sys.stderr.write(r.stdout + r.stderr)
+                print(f"step block={block} batch={batch} failed ({r.returncode}); stopping",
+                      file=sys.stderr)
+                return 1
+            rec = json.loads(r.stdout.strip().splitlines()[-1])
+            steps.append(rec)
+            print(json.dumps(rec), flush=True)
+    doc = {"workload": f"SRC {L}/{M} at {FS} Hz + 6-band EQ (config 3 gains), "
+                       f"{PUSHES} pushes per step after {WARMUP} warm-up pushes",
+           "device": steps[0].pop("device"), "steps": steps}
+    for s in steps[1:]:
+        s.pop("device", None)
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(f"wrote {args.out}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
