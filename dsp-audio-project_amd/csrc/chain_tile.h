@@ -28,6 +28,10 @@ constexpr int kScanRow = 14;  // doubles per row of the blocked carry scan (12 u
 constexpr int kScanPark = 928;
 constexpr int kScanFloats = (kScanPark + 16) * 2;  // its LDS: 64 rows + row 64 + the park row
                                                    // (+4 doubles idle lanes read)
+// The paired tail tile (PairEntry, below) parks a second entry state, that of
+// the upper half's channel, one park row further.
+constexpr int kScanPark2 = 16;
+constexpr int kScanFloatsPair = (kScanPark + 2 * kScanPark2) * 2;
 
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -358,9 +362,13 @@ struct StageBase {
 // is VALU-issue-bound at the power cap).  TS = 32 (round 5): the swizzle of
 // StageBase, free of conflicts both ways (tools/ldsmodel.py --ts32: the padded
 // layout's reads took 32 extra cycles per call) for 8 VALU per call.
-template <int TS>
-__device__ __forceinline__ void store_tile(float* lds, const float (&v)[TS], int lane,
-                                           __amdgpu_buffer_rsrc_t rs) {
+// PAIR (the paired tail tile, PairEntry below): the upper half of the lanes
+// holds another channel's tile; its 32 * TS floats go through `rs1`, from that
+// resource's offset 0.
+template <int TS, bool PAIR>
+__device__ __forceinline__ void store_tile_rs(float* lds, const float (&v)[TS], int lane,
+                                              __amdgpu_buffer_rsrc_t rs,
+                                              __amdgpu_buffer_rsrc_t rs1) {
   constexpr int RS = TS == 32 ? 32 : TS + 4;
   constexpr int NF4 = (kWave / 2) * TS / 4;
   constexpr int NR = (NF4 + kWave - 1) / kWave;  // store rounds per half (the last may be partial)
@@ -395,11 +403,18 @@ __device__ __forceinline__ void store_tile(float* lds, const float (&v)[TS], int
       d.y = __float_as_uint(f.y);
       d.z = __float_as_uint(f.z);
       d.w = __float_as_uint(f.w);
-      __builtin_amdgcn_raw_buffer_store_b128(d, rs, past ? 0x7ffffff0 : (h * (kWave / 2) * TS + g) * 4,
-                                             0, kStream);
+      __builtin_amdgcn_raw_buffer_store_b128(
+          d, PAIR && h ? rs1 : rs,
+          past ? 0x7ffffff0 : ((PAIR ? 0 : h * (kWave / 2) * TS) + g) * 4, 0, kStream);
     }
   }
   fence();
+}
+
+template <int TS>
+__device__ __forceinline__ void store_tile(float* lds, const float (&v)[TS], int lane,
+                                           __amdgpu_buffer_rsrc_t rs) {
+  store_tile_rs<TS, false>(lds, v, lane, rs, rs);
 }
 
 // Entry state of a tile > 0: lane 0 waits for the previous tile of the
@@ -677,6 +692,23 @@ struct EarlyEntry {
 // state and publishes its end state over it (for the repair kernel), no flag.
 struct AggEntry {};
 struct GivenEntry {};
+// k_chain_tile_pair: one wave carries the last tiles of TWO channels, `b` in
+// lanes 0-31 and `b2` in lanes 32-63 (has2: b2 exists; else the upper half
+// runs on zeros and neither stores nor publishes).  Each half is a tile of 32
+// sub-chunks: its own entry state (leader lanes 0 and 32, each with the early
+// poll / LDS-DMA slot / bounded wait of EarlyEntry; half h's slot at slot +
+// 16 h doubles, its park row at park + kScanPark2 h), its own 4-segment scan
+// (segments 4-7 run what segments 0-3 run, nothing crosses from 3 to 4), its
+// own published end state (v_31 of the half: the state after the half's 32
+// sub-chunks, of which those past the row's end hold zeros) and its own y / z
+// resources.  Per lane the arithmetic is the unpaired tile's, so rows are
+// bitwise what a wave of their own gives them.
+struct PairEntry {
+  bool early[2];
+  const double* slot;
+  int64_t b2;
+  bool has2;
+};
 
 template <int TS, bool YST = true, bool REPAIR = false, bool P1F64 = false, class ONNF,
           class ENTRY = ChainedEntry>
@@ -687,6 +719,17 @@ __device__ __forceinline__ void tile_cascade(const TileArgs& a, tt_ptr mt, float
   constexpr bool kEarly = std::is_same_v<std::decay_t<ENTRY>, EarlyEntry>;
   constexpr bool kAgg = std::is_same_v<std::decay_t<ENTRY>, AggEntry>;
   constexpr bool kGiven = std::is_same_v<std::decay_t<ENTRY>, GivenEntry>;
+  constexpr bool kPair = std::is_same_v<std::decay_t<ENTRY>, PairEntry>;
+  // The lane's channel (kPair: the upper half's is entry.b2) and whether it
+  // exists.
+  int hf = 0;
+  int64_t bh = b;
+  bool live = true;
+  if constexpr (kPair) {
+    hf = lane >> 5;
+    bh = hf ? entry.b2 : b;
+    live = !hf || entry.has2;
+  }
   // ---- 2. pass 1: zero-state end state of the sub-chunk
   double v[kD];
   if constexpr (P1F64) pass1_state_f64<TS>(mt, y, v);
@@ -728,6 +771,33 @@ __device__ __forceinline__ void tile_cascade(const TileArgs& a, tt_ptr mt, float
       for (int k = 0; k < kS; ++k)
         *reinterpret_cast<f64x2*>(park + 2 * k) =
             *reinterpret_cast<const f64x2*>(a.states + me * kD + 2 * k);
+    }
+  } else if constexpr (kPair) {
+    // two hand-offs, one per half (leader lanes 0 and 32)
+    const bool leader = (lane & 31) == 0;
+    double* const pk = park + kScanPark2 * hf;
+    const bool mine = tile > 0 && (hf ? entry.early[1] : entry.early[0]);
+    if (tile > 0 && (entry.early[0] || entry.early[1]))
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the LDS-DMA (as EarlyEntry)
+    if (leader && mine) {
+#pragma unroll
+      for (int k = 0; k < kS; ++k)
+        *reinterpret_cast<f64x2*>(pk + 2 * k) =
+            *reinterpret_cast<const f64x2*>(entry.slot + 16 * hf + 2 * k);
+      store_flag(a.flags + bh * a.ntiles + tile - 1, 0u);  // consumed
+    }
+    const bool wait = tile > 0 && leader && live && !mine;
+    if (__builtin_amdgcn_ballot_w64(wait)) {
+      double m_in[kD];
+      tile_entry_state(a, bh, tile, wait ? 0 : 1, m_in);  // (its "lane 0": the waiting leaders)
+      if (wait) {
+#pragma unroll
+        for (int d = 0; d < kD; ++d) pk[d] = m_in[d];
+      }
+    }
+    if (leader && !mine && !wait) {  // tile 0, or no channel in this half
+#pragma unroll
+      for (int k = 0; k < kS; ++k) *reinterpret_cast<f64x2*>(pk + 2 * k) = f64x2{0.0, 0.0};
     }
   } else if (kAgg || tile == 0) {
     if (lane == 0) {
@@ -775,6 +845,10 @@ __device__ __forceinline__ void tile_cascade(const TileArgs& a, tt_ptr mt, float
   // parity on disjoint bank quads (MI355X_MICROARCH.md §LDS; round 3's idle
   // lanes read block 0 of their rows: 32 conflict cycles per wave).
   const int sg = lane >> 3;
+  // kPair: two independent scans of 4 segments; sq is the segment within its
+  // scan, and the Kogge-Stone needs two levels (level 2 reaches no segment).
+  constexpr int kSegs = kPair ? 4 : 8, kLevels = kPair ? 2 : 3;
+  const int sq = kPair ? (sg & 3) : sg;
   const bool worker = (lane & 7) < 6;
   // (idle lanes load the tables of "blocks" 6 and 7 too: entries of Dp's next
   // rows, in bounds, never used for a stored value)
@@ -801,22 +875,22 @@ __device__ __forceinline__ void tile_cascade(const TileArgs& a, tt_ptr mt, float
   // m_in (parked above) enters as segment -1: u_0 += D^(8 TSUB) m_in, and
   // segment 0's entry state is m_in.
   f64x2 mi = f64x2{0.0, 0.0};
-  if (sg == 0) {
-    mi = *reinterpret_cast<const f64x2*>(park + 2 * kb);
+  if (sq == 0) {
+    mi = *reinterpret_cast<const f64x2*>(park + kScanPark2 * hf + 2 * kb);
     u0 = fma(p8a.x, mi.x, fma(p8a.y, mi.y, u0));
     u1 = fma(p8b.x, mi.x, fma(p8b.y, mi.y, u1));
   }
 #pragma unroll
-  for (int lv = 0; lv < 3; ++lv) {
+  for (int lv = 0; lv < kLevels; ++lv) {
     const int dd = 1 << lv;
-    const int ss = sg - dd;
+    const int ss = sq - dd;
     const int src = ss >= 0 ? lane - 8 * dd : lane;
     const double x0 = shfl_f64(u0, src), x1 = shfl_f64(u1, src);
     if (ss >= 0) {
       u0 = fma(p8a.x, x0, fma(p8a.y, x1, u0));
       u1 = fma(p8b.x, x0, fma(p8b.y, x1, u1));
     }
-    if (lv < 2) {  // D^(8 TSUB 2^(lv+1)) = (D^(8 TSUB 2^lv))^2
+    if (lv < kLevels - 1) {  // D^(8 TSUB 2^(lv+1)) = (D^(8 TSUB 2^lv))^2
       const f64x2 qa = f64x2{fma(p8a.x, p8a.x, p8a.y * p8b.x), fma(p8a.x, p8a.y, p8a.y * p8b.y)};
       const f64x2 qb = f64x2{fma(p8b.x, p8a.x, p8b.y * p8b.x), fma(p8b.x, p8a.y, p8b.y * p8b.y)};
       p8a = qa;
@@ -824,7 +898,7 @@ __device__ __forceinline__ void tile_cascade(const TileArgs& a, tt_ptr mt, float
     }
   }
   {
-    const int ss = sg - 1;
+    const int ss = sq - 1;
     const int src = ss >= 0 ? lane - 8 : lane;
     const double x0 = shfl_f64(u0, src), x1 = shfl_f64(u1, src);
     u0 = ss >= 0 ? x0 : mi.x;
@@ -843,10 +917,11 @@ __device__ __forceinline__ void tile_cascade(const TileArgs& a, tt_ptr mt, float
   }
   static_assert(kScanRow == 14, "six blocks and one padding slot per scan row");
   // ---- 4. publish the tile's end state (segment 7's workers hold v_63); the
-  // channel's last tile too, for the repair kernel (no flag: nobody waits)
+  // channel's last tile too, for the repair kernel (no flag: nobody waits).
+  // kPair: segments 3 and 7, each its half's v_31 for its own channel.
   {
-    const int64_t me = b * a.ntiles + tile;
-    if (worker && sg == 7) {
+    const int64_t me = bh * a.ntiles + tile;
+    if (worker && sq == kSegs - 1 && live) {
       store_state(a.states + me * kD + 2 * kb, u0);
       store_state(a.states + me * kD + 2 * kb + 1, u1);
     }
@@ -859,14 +934,15 @@ __device__ __forceinline__ void tile_cascade(const TileArgs& a, tt_ptr mt, float
   // below go out first, so that the wave does not sit in vmcnt(0) on the
   // stores' round trip (round 4): the wait counts the y stores as younger.
   if constexpr (kAgg) return;  // launch 1: the aggregate is all it computes
-  const bool raise = !kRegCarry && !kGiven && tile + 1 < a.ntiles;
+  const bool raise = !kRegCarry && !kGiven && !kPair && tile + 1 < a.ntiles;  // (kPair: last tiles)
   auto raise_flag = [&] {
     if (lane == 8 * 7) store_flag(a.flags + b * a.ntiles + tile, 1u);
   };
   fence();
   double m[kD];
   {
-    const double* src = lane == 0 ? park : rows + lane * kScanRow;
+    const double* src = (kPair ? (lane & 31) == 0 : lane == 0) ? park + kScanPark2 * hf
+                                                               : rows + lane * kScanRow;
 #pragma unroll
     for (int k = 0; k < kS; ++k) {
       const f64x2 t = *reinterpret_cast<const f64x2*>(src + 2 * k);
@@ -880,10 +956,22 @@ __device__ __forceinline__ void tile_cascade(const TileArgs& a, tt_ptr mt, float
   // s = T m, pass 2, z out
   // (the buffer resources start at the tile's first output, so that the store
   // offsets are lane- and k-terms only; their size keeps the row-end checks)
+  // (kPair: the upper half's channel through a resource of its own, empty if
+  // there is no such channel)
+  auto store = [&](float* p, const __amdgpu_buffer_rsrc_t rs, int ln) {
+    if constexpr (kPair) {
+      const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
+          p + (entry.has2 ? entry.b2 : b) * a.ld_y + m0, 0,
+          entry.has2 ? (int)((a.n_out - m0) * 4) : 0, 0x00020000);
+      store_tile_rs<TS, true>(lds, y, ln, rs, rs1);
+    } else {
+      store_tile<TS>(lds, y, ln, rs);
+    }
+  };
   if (YST && a.y) {
     const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
         a.y + b * a.ld_y + m0, 0, (int)((a.n_out - m0) * 4), 0x00020000);
-    store_tile<TS>(lds, y, lane, ry);
+    store(a.y, ry, lane);
     if (raise) {
       // every store but store_tile's TS / 4 (two halves of TS / 8) is done
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(TS / 4) : "memory");
@@ -899,7 +987,7 @@ __device__ __forceinline__ void tile_cascade(const TileArgs& a, tt_ptr mt, float
       a.z + b * a.ld_y + m0, 0, (int)((a.n_out - m0) * 4), 0x00020000);
   int lane_z = lane;
   asm volatile("" : "+v"(lane_z));  // recompute the store offsets (no spill across pass 2)
-  store_tile<TS>(lds, y, lane_z, rz);
+  store(a.z, rz, lane_z);
 }
 
 // Repair kernels (k_chain_*_repair), launched after every single-pass kernel

@@ -78,7 +78,9 @@
 // launch is wrong, nothing hangs.
 //
 // Rows are bitwise independent of the batch size: the geometry depends on
-// (L, M, K) only.
+// (L, M, K) only.  Where a row's last tile fills at most half a wave, the last
+// tiles of two channels share one (k_chain_tile_pair, below): per lane the
+// same arithmetic, so the same rows.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -192,6 +194,120 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(4))) void
   // grid (B, ntiles): linear ids tile-major (x fastest), no division
   const int64_t tile = blockIdx.y, b = blockIdx.x;
   chain_tile_body<GEO, DLY, false>(a, lds, threadIdx.x, b, tile);
+}
+
+// The paired tail tile (chain_tile.h, PairEntry).  A row's last tile often
+// fills under half of its wave (config 3/4: 72000 outputs = 23 tiles + 28 of
+// 64 sub-chunks), and chain_tile_body has no per-lane exit: the idle lanes run
+// the whole tile on zeros.  Here one wave carries the last tiles of channels b
+// (lanes 0-31) and b2 (lanes 32-63), launched after k_chain_tile has run the
+// other ntiles - 1 tiles of every channel (launch_chain_tile).
+//
+// x image: half 0's lanes keep chain_tile_body's windows (lane l at image
+// float 32 l), read from b's row up to image float kXB = 1088, past lane 31's
+// window end 32 * 31 + W = 1064; half 1's windows follow from kXB on (lane
+// 32 + j at kXB + 32 j), read from b2's row at the same xs0.  So no lane of a
+// half ever sees a sample of the other channel, and every lane's window is
+// what it would be in a wave of the channel's own (zeros past the row's end).
+template <class GEO>
+struct PairGeo {
+  // half 0's image, whole 32-float rows of the padding (xpad): 1088 floats
+  static constexpr int XB = (kLS * (kWave / 2 - 1) + GEO::W + 31) / 32 * 32;
+  static_assert(xpad(XB + kLS) - xpad(XB) == 36, "half 1's lane windows 36 floats apart");
+  static constexpr int NWIN = (XB + kLS * (kWave / 2 - 1) + GEO::W + 3) / 4 * 4;
+  static constexpr int XF = xpad(NWIN + 4) + 4;
+  static constexpr int LDSF0 = XF > GEO::LDSF ? XF : GEO::LDSF;
+  static constexpr int LDSF = LDSF0 > kScanFloatsPair ? LDSF0 : kScanFloatsPair;
+  static constexpr int SLOT = kWave;  // floats of the two early slots (16 doubles each, 12 used)
+};
+
+template <class GEO, bool DLY>
+__device__ __forceinline__ void chain_tile_pair_body(const TileArgs& a, float* lds, int lane,
+                                                     int64_t b, int64_t b2, bool has2) {
+  typedef PairGeo<GEO> PG;
+  constexpr int TS = GEO::TSUB;
+  const int64_t tile = a.ntiles - 1;
+  const int64_t m0 = tile * GEO::TILE;
+  const tt_ptr mt = (tt_ptr)a.tt;
+  const int hf = lane >> 5;
+  const int64_t bx = has2 ? b2 : b;  // (no b2: its addresses are b's, never stored to)
+
+  // Early poll of each half's hand-off flag (chain_tile_body), lanes 0 and 32.
+  uint32_t fl = 0;
+  if (tile > 0 && (lane & 31) == 0 && (!hf || has2))
+    fl = load_flag(a.flags + (hf ? b2 : b) * a.ntiles + tile - 1);
+
+  // ---- the two x windows -> one padded LDS image
+  {
+    const __amdgpu_buffer_rsrc_t rx0 = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(a.x) + b * a.ld_x, 0, (int)(a.n_in * 4), 0x00020000);
+    // (no second channel: an empty resource, every load gives zeros)
+    const __amdgpu_buffer_rsrc_t rx1 = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(a.x) + bx * a.ld_x, 0, has2 ? (int)(a.n_in * 4) : 0, 0x00020000);
+    const int64_t xs0 = m0 * GEO::M / GEO::L + a.cq - (GEO::TT - 1);  // multiple of 4
+    constexpr int NF = PG::NWIN / 4, NA = PG::XB / 4;
+    const int off0 = (int)(xs0 * 4) + 16 * lane;
+    float* const l0 = lds + 4 * lane + 4 * (lane >> 3);
+#pragma unroll
+    for (int k = 0; k < (NF + kWave - 1) / kWave; ++k) {
+      // float4 f = lane + 64 k of the image: b's row below NA, b2's from NA on
+      const int f = lane + kWave * k;
+      if (k * kWave < NA && ((k + 1) * kWave <= NA || f < NA)) {
+        const f32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rx0, off0 + 1024 * k, 0, kStream);
+        *reinterpret_cast<f32x4*>(l0 + 288 * k) = v;
+      }
+      if ((k + 1) * kWave > NA && (k * kWave >= NA || f >= NA) &&
+          ((k + 1) * kWave <= NF || f < NF)) {
+        const f32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rx1, off0 + 1024 * k - 4 * PG::XB, 0,
+                                                              kStream);
+        *reinterpret_cast<f32x4*>(l0 + 288 * k) = v;
+      }
+    }
+  }
+  fence();
+  PairEntry entry{{false, false}, reinterpret_cast<const double*>(lds + PG::LDSF), b2, has2};
+  if (tile > 0) {
+    entry.early[0] = __builtin_amdgcn_readlane(fl, 0) == 1u;
+    entry.early[1] = __builtin_amdgcn_readlane(fl, 32) == 1u;
+    if (entry.early[0] || entry.early[1]) {
+      // One LDS-DMA of all 64 lanes (the destination is the slot + 4 lane
+      // bytes): lane 32 h + j brings dword j of half h's state, j < 24; the
+      // other lanes repeat dwords 0-7 into the slot's unused tail.  A half
+      // whose flag was not up yet loads too and ignores what it got.
+      const int64_t prev = (hf ? bx : b) * a.ntiles + tile - 1;
+      const int j = lane & 31;
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) void*)(reinterpret_cast<const uint32_t*>(
+                                                               a.states + prev * kD) +
+                                                           (j < 2 * kD ? j : j - 2 * kD)),
+          (__attribute__((address_space(3))) void*)(lds + PG::LDSF), 4, 0, kSc1);
+    }
+  }
+
+  // ---- 1. SRC (chain_tile_body's): half 1's windows start at image float XB
+  float y[TS];
+  {
+    const float* xw = lds + 36 * lane + hf * (xpad(PG::XB) - 36 * (kWave / 2));
+    static_assert(TS == 48, "SRC parts of 48 / 24 outputs");
+    if constexpr (DLY) {
+      src_part<GEO, 0, 48, true>(xw, mt, y);
+      pin(y);
+    } else {
+      src_part<GEO, 0, 24, false>(xw, mt, y);
+      pin(y);
+      src_part<GEO, 24, 24, false>(xw, mt, y);
+      pin(y);
+    }
+  }
+  tile_cascade<TS>(a, mt, lds, y, lane, b, tile, m0, 0, entry);
+}
+
+template <class GEO, bool DLY = false>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(4))) void
+k_chain_tile_pair(TileArgs a) {
+  __shared__ __attribute__((aligned(16))) float lds[PairGeo<GEO>::LDSF + PairGeo<GEO>::SLOT];
+  const int64_t b = 2 * (int64_t)blockIdx.x;
+  chain_tile_pair_body<GEO, DLY>(a, lds, threadIdx.x, b, b + 1, b + 1 < a.B);
 }
 
 // Launches 1 and 3 of the three-launch mode (chain_tile.h, AggEntry).
@@ -1538,7 +1654,19 @@ int launch_chain_tile(const float* x, float* y, float* z, int64_t B, int64_t n_i
     } else {
       TraceScope trace("chain_tile", s);
       auto kern = dly ? k_chain_tile<Geo3241, true> : k_chain_tile<Geo3241, false>;
-      hipLaunchKernelGGL(kern, grid, dim3(kWave), 0, s, a);
+      // A last tile of at most 32 sub-chunks (half a wave): the last tiles of
+      // two channels share a wave (k_chain_tile_pair), after the other tiles
+      // of every channel.  a.ntiles stays: tile ntiles - 2 raises its flag.
+      const int64_t tail = n_out - (tp.ntiles - 1) * Geo3241::TILE;
+      if (B >= 2 && ceil_div(tail, (int64_t)Geo3241::TSUB) <= kWave / 2) {
+        if (tp.ntiles > 1)
+          hipLaunchKernelGGL(kern, dim3((unsigned)B, (unsigned)(tp.ntiles - 1)), dim3(kWave), 0, s,
+                             a);
+        auto pair = dly ? k_chain_tile_pair<Geo3241, true> : k_chain_tile_pair<Geo3241, false>;
+        hipLaunchKernelGGL(pair, dim3((unsigned)ceil_div(B, 2)), dim3(kWave), 0, s, a);
+      } else {
+        hipLaunchKernelGGL(kern, grid, dim3(kWave), 0, s, a);
+      }
     }
     TraceScope trace("chain_repair", s);
     auto rep = dly ? k_chain_tile_repair<Geo3241, true> : k_chain_tile_repair<Geo3241, false>;
