@@ -9,9 +9,16 @@ sample at Qc(i) + UC -- must reproduce the reference's SRC
 for every L, M in 1..8 of the app's sliders (app.py:149-150) at the default
 tap rule, for config 1's 2/1 at K = 127 and for the SRC bypass as the one-tap
 SRC (L = M = 1, K = 1: y = x, dsp_core.py:144-145).  This pins the host's slot /
-shift / alignment algebra independently of the GPU."""
+shift / alignment algebra independently of the GPU.
+
+Also rows shorter than the filter (n_in L < K) and ratios outside the sliders
+that reduce to a listed geometry (10/5 ... 64/56), wherever the host picks a
+per-phase kernel: they reach alignments A, carries r0 and residues rho = c mod
+gcd(L, M) != 0 that no long slider row has.  tests/test_gpu_pp_edges.py runs
+the same cases on the GPU and takes its case lists and length rules from here."""
 import math
 import os
+import re
 
 import numpy as np
 import pytest
@@ -31,6 +38,78 @@ def _entries():
     return rows
 
 
+def _entry_ratios():
+    """The representative (L, M, K) of every entry: the first ratio of its
+    line's comment in chain_pp_list.h, in entry order."""
+    out = []
+    with open(LIST) as f:
+        for line in f:
+            if line.startswith("PP_GEO("):
+                m = re.search(r"//\s*(\d+)/(\d+):K(\d+)", line)
+                assert m, line
+                out.append(tuple(int(v) for v in m.groups()))
+    return out
+
+
+def _n_out(n_in, L, M, K):
+    """Outputs of an n_in-sample row (design.src_plan: ceil(max(n_in L, K) / M))."""
+    return -(-max(n_in * L, K) // M)
+
+
+def _short_lengths(L, K):
+    """Rows shorter than the filter (n_in L < K): 4 samples and the largest
+    multiple of 4."""
+    top = (K - 1) // L
+    top -= top % 4
+    assert top >= 4 and top * L < K <= (top + 4) * L
+    return sorted({4, top})
+
+
+def _ragged_length(L, M, K, ts, tiles=2):
+    """n_in (a multiple of 4) whose n_out fills `tiles` tiles of 64 ts outputs
+    and about a third of the next, with n_out off every multiple of 4 and of
+    ts where the ratio allows it (integer upsampling, M / gcd = 1, cannot:
+    n_out = n_in L / M is a multiple of 4 then)."""
+    tile = 64 * ts
+    lo, hi = tiles * tile + tile // 3, (tiles + 1) * tile
+    n_in = -(-lo * M // L)
+    n_in += -n_in % 4
+    first = n_in
+    while _n_out(n_in, L, M, K) < hi:
+        n_out = _n_out(n_in, L, M, K)
+        if n_out % 4 and n_out % ts:
+            return n_in
+        n_in += 4
+    return first
+
+
+# Ratios outside the app's sliders whose reduced ratio is a listed geometry
+# (tile_geometry_any admits L, M <= 64), at the default tap rule.
+NON_SLIDER = [(10, 5), (9, 3), (12, 8), (64, 32), (16, 24), (24, 16), (40, 8), (8, 40), (56, 64),
+              (64, 56), (33, 11)]
+SLIDER = [(L, M) for L in range(1, 9) for M in range(1, 9) if (L, M) != (1, 1)]
+
+
+def _gains():
+    from oracle import dsp_ref_cpu as orc
+    return orc.CONFIG3_GAINS
+
+
+def _host_answer(lib, plan, n_in):
+    """What the host says of a call: (tile length or 0, the tables or None,
+    the per-phase entry index or -1).  A per-phase kernel serves the call
+    where the tables carry tap rows (pp_np > 0)."""
+    sos = np.ascontiguousarray(design.eq_plan(plan.fs_out, _gains()).sos)
+    ts = int(lib.dsp_chain_tile_len(n_in, plan.n_out, plan.K, plan.L, plan.M, plan.c_offset,
+                                    sos.shape[0]))
+    if ts <= 0:
+        return 0, None, -1
+    rc, tb = _tables(lib, plan, n_in, sos)
+    if rc != 0:
+        return 0, None, -1
+    return ts, tb, (int(tb["pp_geo"]) if int(tb["pp_np"]) > 0 else -1)
+
+
 def _tables(lib, plan, n_in, sos):
     from test_abi import _tables_dtype
     import ctypes
@@ -44,16 +123,22 @@ def _tables(lib, plan, n_in, sos):
     return rc, buf.view(_tables_dtype())[0]
 
 
+def _xa0(plan):
+    """First window sample of tile 0 (pp_need's xa0): w0 = c1 div L' - (T - 1)
+    rounded down to a multiple of 4, c1 = c div gcd(L, M); negative where the
+    window starts before the row."""
+    g = math.gcd(plan.L, plan.M)
+    T = -(-plan.K // plan.L)
+    w0 = (plan.c_offset // g) // (plan.L // g) - (T - 1)
+    return w0 - (w0 % 4)
+
+
 def _model_y(x, plan, tb, entry):
     """y of the kernel's SRC from the tables, in float64 (the kernel's float32
     pairs agree to rounding)."""
     _, LR, MR, TS, NP, UC, _, _ = entry
-    L, M, K, c = plan.L, plan.M, plan.K, plan.c_offset
-    g = math.gcd(L, M)
-    T = -(-K // L)
-    c1 = c // g
-    w0 = c1 // LR - (T - 1)
-    xa0 = w0 - (w0 % 4)
+    K = plan.K
+    xa0 = _xa0(plan)
     LS = TS * MR // LR
     P = 2 * LR if MR % 2 else LR
     tpw = tb["tpw"][:P * NP * 2].astype(np.float64).reshape(P, 2 * NP)
@@ -101,3 +186,67 @@ def test_pp_tables_reproduce_reference_src(L, M, K):
     got = _model_y(x.astype(np.float64), plan, tb, entry)
     assert got.shape == ref.shape
     np.testing.assert_allclose(got, ref, rtol=0, atol=2e-6 * max(1.0, np.abs(ref).max()))
+
+
+def _need(plan):
+    """(A, r0, rho) of pp_need (csrc/chain_tile.hip): the window's float4
+    alignment, the first output's branch carry and c mod gcd(L, M)."""
+    g = math.gcd(plan.L, plan.M)
+    c1 = plan.c_offset // g
+    w0 = c1 // (plan.L // g) - (-(-plan.K // plan.L) - 1)
+    return w0 % 4, c1 % (plan.L // g), plan.c_offset % g
+
+
+def _edge_lengths(L, M):
+    """Rows shorter than the filter for every ratio; for the ratios outside
+    the sliders a long row as well."""
+    K = design.default_num_taps(L, M)
+    return _short_lengths(L, K) + ([1536] if (L, M) in NON_SLIDER else [])
+
+
+# Short rows and non-slider ratios a per-phase kernel must serve (so that the
+# cases below cannot quietly check nothing), with what each is there for.
+MUST_SERVE = [(2, 4, 4), (3, 5, 4), (16, 24, 4), (56, 64, 4)] + [(L, M, 1536) for L, M in NON_SLIDER]
+
+
+@pytest.mark.parametrize("L,M", SLIDER + NON_SLIDER, ids=[f"{L}/{M}" for L, M in SLIDER + NON_SLIDER])
+def test_pp_tables_short_rows_and_reduced_ratios(L, M):
+    """Rows shorter than the filter (n_in L < K: c = (n_in L - 1) // 2, n_out =
+    ceil(K / M)) and ratios outside the sliders that reduce to a listed
+    geometry, wherever the host picks a per-phase kernel: alignments A, carries
+    r0 and residues rho = c mod gcd(L, M) that no long slider row has (there
+    rho = 0), against the reference's SRC."""
+    from oracle import dsp_ref_cpu as orc
+    lib = _lib.load()
+    served = []
+    for n_in in _edge_lengths(L, M):
+        plan = design.src_plan(n_in, 48000, M, L, None)
+        ts, tb, pe = _host_answer(lib, plan, n_in)
+        if (L, M, n_in) in MUST_SERVE:
+            assert pe >= 0, f"{L}/{M} at n_in = {n_in}: no per-phase kernel (tile_len {ts})"
+        if pe < 0:
+            continue
+        entry = _entries()[pe]
+        g = math.gcd(L, M)
+        assert entry[1:4] == (L // g, M // g, ts) and int(tb["pp_np"]) == entry[4]
+        x = np.random.default_rng(L * 100 + M + n_in).uniform(-1, 1, n_in).astype(np.float32)
+        ref, _ = orc.resample(x.astype(np.float64), 48000, M, L, None)
+        got = _model_y(x.astype(np.float64), plan, tb, entry)
+        assert got.shape == ref.shape
+        err = float(np.max(np.abs(got - ref)))
+        tol = 2e-6 * max(1.0, float(np.abs(ref).max()))
+        served.append((n_in, pe) + _need(plan) + (err,))
+        assert err <= tol, (L, M, n_in, pe, _need(plan), err, tol)
+    print(f"{L}/{M}: (n_in, entry, A, r0, rho, err) {served}")
+
+
+def test_pp_short_rows_reach_new_alignments():
+    """What the short rows are there for: 2/4 at 4 samples has rho = 1, 16/24
+    rho = 7, 3/5 (A, r0) = (3, 2) where its long rows have (3, 1); every long
+    slider row has rho = 0."""
+    assert _need(design.src_plan(4, 48000, 4, 2))[2] == 1
+    assert _need(design.src_plan(4, 48000, 24, 16))[2] == 7
+    assert _need(design.src_plan(4, 48000, 5, 3))[:2] == (3, 2)
+    assert _need(design.src_plan(1536, 48000, 5, 3))[:2] == (3, 1)
+    for L, M in SLIDER:
+        assert _need(design.src_plan(1536, 48000, M, L))[2] == 0, (L, M)
