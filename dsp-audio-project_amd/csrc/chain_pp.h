@@ -330,9 +330,15 @@ struct PpEntry {
   int LR, MR, TS, NP, UC, NH, PB;
 };
 
-// Launch 2 of the three-launch mode (chain_tile.hip): the aggregates in
-// states[] scanned into the tiles' entry states, per channel.
-void launch_tile_carry(const TileArgs& a, int tile_len, hipStream_t s);
+// The launch sequences every single-pass kernel family shares (chain_tile.hip):
+// the three-launch mode -- `agg` (launch 1, the tiles' aggregates), the carry
+// scan of states[] into the tiles' entry states, then `given` (launch 3) -- and
+// the repair kernel that follows either mode.  shm: dynamic LDS bytes.
+typedef void (*TileKernel)(TileArgs);
+int launch_three(TileKernel agg, TileKernel given, dim3 grid, unsigned block, size_t shm,
+                 const TileArgs& a, hipStream_t s);
+int launch_repair(TileKernel rep, unsigned rgrid, unsigned block, size_t shm, const TileArgs& a,
+                  hipStream_t s);
 
 // Launches k_chain_pp<G> (three: the three-launch mode instead) and its
 // repair kernel on s (the caller checked the geometry, tables
@@ -341,19 +347,12 @@ template <class G>
 int pp_launch(const TileArgs& a, unsigned rgrid, bool three, hipStream_t s) {
   const dim3 grid((unsigned)a.B, (unsigned)a.ntiles);
   if (three) {
-    {
-      TraceScope trace("chain_tile_agg", s);
-      hipLaunchKernelGGL((k_chain_pp3<G, 1>), grid, dim3(kWave), 0, s, a);
-    }
-    launch_tile_carry(a, G::TS, s);
-    TraceScope trace("chain_tile", s);
-    hipLaunchKernelGGL((k_chain_pp3<G, 2>), grid, dim3(kWave), 0, s, a);
+    if (int rc = launch_three(k_chain_pp3<G, 1>, k_chain_pp3<G, 2>, grid, kWave, 0, a, s)) return rc;
   } else {
     TraceScope trace("chain_tile", s);
     hipLaunchKernelGGL(k_chain_pp<G>, grid, dim3(kWave), 0, s, a);
   }
-  TraceScope trace("chain_repair", s);
-  hipLaunchKernelGGL(k_chain_pp_repair<G>, dim3(rgrid), dim3(kWave), 0, s, a);
+  if (int rc = launch_repair(k_chain_pp_repair<G>, rgrid, kWave, 0, a, s)) return rc;
   DSP_LAUNCHED("k_chain_pp");
   return DSP_OK;
 }

@@ -303,7 +303,8 @@ int launch_quantize_pcm16(const float* z, int16_t* out, int64_t B, int64_t n, in
 int xstate_geometry(int64_t chunk_len, int K, int L, int M, int64_t c, int64_t* shift,
                     int64_t* q0, int64_t* rows, int64_t* span = nullptr);
 // Single-pass chain (chain_tile.hip): y = SRC(x) and z = clip(cascade(y)) in
-// one launch, y never re-read.  chain_tile_sub returns the sub-chunk length of
+// one launch, y never re-read.  The queries and the tables are the host
+// planner's (chain_plan.hip).  chain_tile_sub returns the sub-chunk length of
 // the instantiated geometry (0: the two-launch chain serves this call).
 int64_t chain_tile_sub(int64_t n_in, int64_t n_out, int K, int L, int M, int64_t c, int S);
 // The path dsp_chain_f32's default takes for a batch of B rows (0 two-launch,

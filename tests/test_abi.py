@@ -253,7 +253,7 @@ def test_chain_status_spin_limit_and_null_y_validation():
 
 
 def _tables_dtype():
-    """numpy mirror of csrc/chain_tile.hip's TileTables (C layout)."""
+    """numpy mirror of csrc/chain_tile.h's TileTables (C layout)."""
     import numpy as np
     return np.dtype([("key", "<u8"), ("G", "<f8", (64, 12)), ("Gc", "<f4", (32, 12, 2)),
                      ("Q", "<f8", (12, 12)), ("Dp", "<f8", (6, 6, 2, 2)), ("T", "<f8", (12, 12)),

@@ -407,6 +407,42 @@ def test_three_launch_mode_generic_kernels(gpu, fs, L, M, K, B, n_in):
         assert np.max(np.abs(m0[b].cpu().numpy() - rmag)) <= MAG_RTOL * np.max(rmag)
 
 
+def test_forced_persistent_path_variant_table(gpu):
+    """dsp_chain_path 3 asks for the persistent kernel, which only the 160/147
+    kernels have.  On the other kinds it stays automatic: one 48000-sample
+    row of 3/2 (k_chain_tile), 2/1 (k_chain_pp) and 7/3 at K = 55
+    (k_chain_gen) takes the three-launch mode as under path 0, the same
+    launches and bitwise the same y and z.  On 160/147 it never takes three
+    launches, where path 0 does for this row; z then agrees within 2e-6 (the
+    carries sum in another order)."""
+    from dspcore.chain import Chain, ChainConfig
+    from oracle import dsp_ref_cpu as orc
+    n_in = 48000
+    for L, M, K in ((3, 2, None), (2, 1, None), (7, 3, 55)):
+        ch = Chain(ChainConfig(n_in, 48000, L, M, K, orc.CONFIG3_GAINS, n_fft=2048), 1, gpu)
+        assert ch.tile_len > 0
+        gen = torch.Generator(device=gpu).manual_seed(3 * L + M)
+        x = torch.rand((1, n_in), generator=gen, device=gpu) * 2 - 1
+        (y0, z0, _), names0 = _traced(lambda: ch.run(x))
+        with _chain_path(3):
+            (y3, z3, _), names3 = _traced(lambda: ch.run(x))
+        assert names3 == names0 and "chain_tile_agg" in names3, (L, M, names0, names3)
+        assert torch.equal(y3, y0) and torch.equal(z3, z0), (L, M)
+        assert ch.handoff_ok()
+    ch = Chain(ChainConfig(n_in, 44100, 160, 147, 1023, orc.CONFIG3_GAINS, n_fft=2048), 1, gpu)
+    assert ch.tile_len == 32
+    gen = torch.Generator(device=gpu).manual_seed(160)
+    x = torch.rand((1, n_in), generator=gen, device=gpu) * 2 - 1
+    (y0, z0, _), names0 = _traced(lambda: ch.run(x))
+    with _chain_path(3):
+        (y3, z3, _), names3 = _traced(lambda: ch.run(x))
+    assert names0.count("chain_tile_agg") == 1, names0
+    assert "chain_tile_agg" not in names3 and "chain_tile" in names3, names3
+    assert torch.equal(y3, y0)
+    assert (z3 - z0).abs().max().item() <= 2e-6
+    assert ch.handoff_ok()
+
+
 def test_drop_in_equaliser_handoff_give_up_falls_back(gpu):
     """The drop-in's single-pass cascade reads the hand-off status for numpy
     calls: with every wait giving up at once (spin limit 0, chained tiles

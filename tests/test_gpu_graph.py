@@ -32,7 +32,7 @@ CHAIN_MAG_RTOL = 1e-5
 
 def _flag_region(ch):
     """(offset, bytes) of the hand-off flag array in Chain's workspace: the
-    layout of csrc/chain_tile.hip tile_ws() -- a 256-byte status header, the
+    layout of csrc/chain_plan.hip tile_ws() -- a 256-byte status header, the
     [B][ntiles][12] float64 end states, then [B][ntiles] uint32 flags, each
     region 256-byte aligned."""
     tile = 64 * ch.tile_len

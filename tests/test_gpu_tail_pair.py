@@ -68,7 +68,7 @@ def _chain(gpu, n_in, B, keep_y=True):
 
 
 def _layout(ch):
-    """(ntiles, offset of the flag array, its bytes): csrc/chain_tile.hip
+    """(ntiles, offset of the flag array, its bytes): csrc/chain_plan.hip
     tile_ws(), read as tests/test_gpu_graph.py does."""
     ntiles = -(-ch.n_out // (64 * ch.tile_len))
     off = 256 + ((ch.B * ntiles * 12 * 8 + 255) & ~255)

@@ -321,7 +321,7 @@ def _chain_input(name, tile_len):
 
 
 def _last_tile_states(ch):
-    """Published end state of every channel's last tile (csrc/chain_tile.hip
+    """Published end state of every channel's last tile (csrc/chain_plan.hip
     tile_ws(): 256-byte header, then [B][ntiles][12] float64)."""
     ntiles = _ceil(ch.n_out, WAVE * ch.tile_len)
     st = ch.workspace[256:256 + ch.B * ntiles * 96].view(torch.float64).reshape(ch.B, ntiles, 12)

@@ -84,7 +84,7 @@ def _ragged_length(L, M, K, ts, tiles=2):
 
 
 # Ratios outside the app's sliders whose reduced ratio is a listed geometry
-# (tile_geometry_any admits L, M <= 64), at the default tap rule.
+# (tile_geometry admits L, M <= 64), at the default tap rule.
 NON_SLIDER = [(10, 5), (9, 3), (12, 8), (64, 32), (16, 24), (24, 16), (40, 8), (8, 40), (56, 64),
               (64, 56), (33, 11)]
 SLIDER = [(L, M) for L in range(1, 9) for M in range(1, 9) if (L, M) != (1, 1)]
@@ -189,7 +189,7 @@ def test_pp_tables_reproduce_reference_src(L, M, K):
 
 
 def _need(plan):
-    """(A, r0, rho) of pp_need (csrc/chain_tile.hip): the window's float4
+    """(A, r0, rho) of pp_need (csrc/chain_plan.hip): the window's float4
     alignment, the first output's branch carry and c mod gcd(L, M)."""
     g = math.gcd(plan.L, plan.M)
     c1 = plan.c_offset // g

@@ -8,7 +8,7 @@ mkdir -p ../build/var
 flags="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -I. -fno-slp-vectorize -DPP_LIST=\"$list\""
 objs=""
 for f in abi src_poly iir fft fft_nf lfilter_nf audio_io; do objs="$objs ../build/$f.o"; done
-for f in chain_tile chain_pp_0 chain_pp_1 chain_pp_2 chain_pp_3; do
+for f in chain_plan chain_tile chain_pp_0 chain_pp_1 chain_pp_2 chain_pp_3; do
   /opt/rocm/bin/hipcc $flags -c $f.hip -o ../build/var/${f}_$name.o &
   objs="$objs ../build/var/${f}_$name.o"
 done

@@ -81,10 +81,12 @@ def main(names):
         f.write(hdr)
     with open(src, "w") as f:
         f.write(hip)
-    # chain_pp.h next to the patched header, so that its "chain_tile.h" is that one
-    shutil.copy(os.path.join(CSRC, "chain_pp.h"), os.path.join(BUILD, "var", "chain_pp.h"))
+    # chain_pp.h and chain_plan.h next to the patched header, so that their
+    # "chain_tile.h" is that one
+    for h in ("chain_pp.h", "chain_plan.h"):
+        shutil.copy(os.path.join(CSRC, h), os.path.join(BUILD, "var", h))
     others = [os.path.join(BUILD, f"{n}.o") for n in
-              ("abi", "src_poly", "iir", "chain_pp_0", "chain_pp_1", "chain_pp_2", "chain_pp_3",
+              ("abi", "src_poly", "iir", "chain_plan", "chain_pp_0", "chain_pp_1", "chain_pp_2", "chain_pp_3",
                "fft", "fft_nf", "lfilter_nf", "audio_io")]
     procs = []
     for name in names:
