@@ -92,7 +92,8 @@ __device__ __forceinline__ double decode(const uint8_t* __restrict__ p) {
 }
 
 // np.add.reduce over a contiguous axis of length ch, then / ch: a plain loop
-// below 8 elements, numpy's 8-accumulator pairwise block up to 128.
+// below 8 elements, numpy's 8-accumulator pairwise block up to 128.  Mono takes
+// no mean (the reference's array is 1-D) and stays as decoded.
 template <int FMT, int BITS, bool BE, bool S8>
 __device__ __forceinline__ double channel_mean(const uint8_t* __restrict__ f, int ch) {
   constexpr int W = BITS / 8;
@@ -113,7 +114,9 @@ __device__ __forceinline__ double channel_mean(const uint8_t* __restrict__ f, in
     s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
     for (; c < ch; ++c) s += decode<FMT, BITS, BE, S8>(f + c * W);
   }
-  return s / (double)ch;
+  // numpy's reduction starts from the identity, +0.0: a frame of all -0.0 sums
+  // to +0.0 (IEEE: -0.0 + 0.0 = +0.0; no other sum changes).
+  return (s + 0.0) / (double)ch;
 }
 
 template <int FMT, int BITS, bool BE, bool S8>

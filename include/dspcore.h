@@ -386,7 +386,9 @@ int dsp_chain_f32(const float* x, float* y, float* z, float* mag, int64_t B,
  *                        float32 [B][ld_out]: each sample scaled as soundfile
  *                        returns it (float64: ints / 2^(bits-1), u8 - 128,
  *                        G.711 expanded to 16-bit linear / 2^15), the
- *                        channel mean in float64 in numpy's summation order,
+ *                        channel mean in float64 in numpy's summation order
+ *                        (started from +0.0, so a frame of all -0.0 gives
+ *                        +0.0; one channel is passed through as decoded),
  *                        rounded to float32 (bit-identical to the reference);
  *   dsp_peak_normalize_f32  DEVICE: per row, peak = max|x| (float32; a NaN
  *                        propagates like np.max) and x /= peak where
