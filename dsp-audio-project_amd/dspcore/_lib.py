@@ -38,7 +38,8 @@ _c_i32, _c_i64, _c_u64, _c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64,
 _vp, _dp = ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)
 
 # name -> (restype, argtypes); mirrors include/dspcore.h one to one, then
-# include/dspcore_stream.h.  load() requires every one to be exported.
+# include/dspcore_stream.h and include/dspcore_eqbank.h.  load() requires every
+# one to be exported.
 _SIGNATURES = {
     "dsp_version": (ctypes.c_int, []),
     "dsp_last_error": (ctypes.c_char_p, []),
@@ -106,10 +107,20 @@ _SIGNATURES = {
         _c_i32, _c_i32, _c_i32, _c_i64, _c_i64, _c_i64, _c_i32, ctypes.POINTER(_c_i64),
         ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64)]),
     "dsp_stream_roll_f32": (ctypes.c_int, [_vp, _c_i64, _c_i64, _c_i64, _c_i64, _vp]),
+    # include/dspcore_eqbank.h
+    "dsp_eqbank_version": (ctypes.c_int, []),
+    "dsp_eqbank_bytes": (_c_sz, [_c_i32]),
+    "dsp_eqbank_build": (ctypes.c_int, [_vp, _c_sz, _dp, _vp, _vp, _c_i32, _c_i32, _c_i64]),
+    "dsp_eqbank_cascade_f32": (ctypes.c_int, [
+        _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _c_sz, _c_i32, _c_i32, _c_i64, _vp, _vp,
+        _vp, _c_i64, _vp]),
 }
 STREAM_HEADER_PATH = os.path.join(REPO_ROOT, "include", "dspcore_stream.h")
 DSP_STREAM_MAX_STAGES = 8
 DSP_STREAM_MAX_HIST = 4096
+EQBANK_HEADER_PATH = os.path.join(REPO_ROOT, "include", "dspcore_eqbank.h")
+DSP_EQBANK_MAX_STAGES = 8
+DSP_EQBANK_RECORD_BYTES = 2816
 DSP_TRACE_NAME = 32
 DSP_WAV_PCM = 1
 DSP_WAV_FLOAT = 3

@@ -22,6 +22,7 @@ import torch
 from . import _lib, ops
 from .chain import ROW_ALIGN
 from .design import caller_taps, eq_plan, stream_src_plan
+from .eqbank import EqBank
 
 
 def _pitch(n: int) -> int:
@@ -43,9 +44,16 @@ class StreamChain:
     The EQ state belongs to the cascade it was filtered with: changing the
     gains mid-stream would click, so a new plan means a new StreamChain (or
     reset()).  With every |gain| < 0.1 the reference bypasses the EQ and z is
-    y (no clip, dsp_core.py:222-223)."""
+    y (no clip, dsp_core.py:222-223).
 
-    def __init__(self, fs: int, L: int, M: int, num_taps: int | None, gains: dict, batch: int,
+    `gains` is one dict for every channel, or a sequence of `batch` dicts, one
+    per channel: the cascade is then an EqBank (dspcore.eqbank, one launch,
+    `iir_bank`, in place of `iir_stream`) with max_n = the longest block the
+    SRC can produce, the state tensor is [batch, 2 * (the largest stage
+    count)], and a channel whose own plan is the bypass gets z = y in its
+    rows of the one z buffer."""
+
+    def __init__(self, fs: int, L: int, M: int, num_taps: int | None, gains, batch: int,
                  max_block: int, device: torch.device | str = "cuda", keep_y: bool = True):
         ops.require_gpu()
         self.B = int(batch)
@@ -78,6 +86,17 @@ class StreamChain:
             self._ldx = _pitch(self.hist + self.max_block + 1)
             self._xs = torch.zeros((self.B, self._ldx), dtype=torch.float32, device=dev)
             self._ybuf = torch.empty((self.B, _pitch(max_out)), dtype=torch.float32, device=dev)
+        self.bank = None
+        if not isinstance(gains, dict):
+            # one gains dict per channel: the EQ bank (dspcore.eqbank), whose
+            # chunking is fixed by the longest block the SRC can hand it
+            self.eq = self.sos = None
+            self.bank = EqBank(self.fs_out, gains, max_out, dev, batch=self.B)
+            self._zbuf = torch.empty((self.B, _pitch(max_out)), dtype=torch.float32, device=dev)
+            self._state = torch.zeros((self.B, max(2 * self.bank.max_stages, 2)),
+                                      dtype=torch.float64, device=dev)
+            self.reset()
+            return
         self.eq = eq_plan(self.fs_out, gains)
         self.sos = np.ascontiguousarray(self.eq.sos, dtype=np.float64)
         S = self.sos.shape[0]
@@ -132,6 +151,11 @@ class StreamChain:
         return c.value, n.value
 
     def _eq(self, y: torch.Tensor) -> torch.Tensor:
+        if self.bank is not None:
+            z = self._zbuf[:, :y.shape[1]]
+            if y.shape[1]:
+                self.bank.apply(y, zi=self._state, out=z, zf=self._state)
+            return z
         if self.eq.bypass:
             return y
         z = self._zbuf[:, :y.shape[1]]
