@@ -100,17 +100,26 @@ __host__ __device__ inline void cascade_state_step(const SosParams& p, int S, bo
   }
 }
 
-// A of the D = 2S state system, float64, row-major.
-inline std::vector<double> state_matrix(const SosParams& p, int S) {
-  const int D = 2 * S;
+// A of a D-state linear system, float64, row-major, from its step function
+// step(X, u): X <- A X + B u (column c is the step of the unit state e_c with
+// u = 0).  Any realisation: the direct form II above, or the transposed form
+// of the live EQ (iir_live.hip).
+template <class STEP>
+inline std::vector<double> state_matrix(int D, STEP step) {
   std::vector<double> A((size_t)D * D, 0.0);
   for (int col = 0; col < D; ++col) {
     std::vector<double> X(D, 0.0);
     X[col] = 1.0;
-    cascade_state_step(p, S, false, X.data(), 0.0);
+    step(X.data(), 0.0);
     for (int r = 0; r < D; ++r) A[(size_t)r * D + col] = X[r];
   }
   return A;
+}
+
+// A of the D = 2S state system of the direct form II realisation `p`.
+inline std::vector<double> state_matrix(const SosParams& p, int S) {
+  return state_matrix(2 * S,
+                      [&](double* X, double u) { cascade_state_step(p, S, false, X, u); });
 }
 
 inline std::vector<double> matmul(const std::vector<double>& a, const std::vector<double>& b,
@@ -125,16 +134,20 @@ inline std::vector<double> matmul(const std::vector<double>& a, const std::vecto
   return c;
 }
 
-// A^T by square-and-multiply (the state transition across T samples).
-inline std::vector<double> chunk_transition(const SosParams& p, int S, int64_t T) {
-  const int D = 2 * S;
-  std::vector<double> base = state_matrix(p, S), r((size_t)D * D, 0.0);
+// A^T by square-and-multiply (the state transition across T samples) of the
+// D x D one-step matrix A.
+inline std::vector<double> chunk_transition(std::vector<double> base, int D, int64_t T) {
+  std::vector<double> r((size_t)D * D, 0.0);
   for (int i = 0; i < D; ++i) r[(size_t)i * D + i] = 1.0;
   for (int64_t e = T; e > 0; e >>= 1) {
     if (e & 1) r = matmul(r, base, D);
     if (e > 1) base = matmul(base, base, D);
   }
   return r;
+}
+
+inline std::vector<double> chunk_transition(const SosParams& p, int S, int64_t T) {
+  return chunk_transition(state_matrix(p, S), 2 * S, T);
 }
 
 }  // namespace dsp

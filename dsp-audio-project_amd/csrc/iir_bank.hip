@@ -97,12 +97,13 @@ __global__ __launch_bounds__(kWave) void k_iir_bank(const float* x, float* y, in
     for (int j = 0; j < 5; ++j) p.c[k][j] = rec->p.c[k][j];
   }
   p.G = rec->p.G;
-  stream_row<S, true>(xr, yr, tile, n, T, C, lane, p, clip, zi ? zi + b * ld_state : nullptr,
-                      zf_row, 2 * stages, vec_x, vec_y, [&](double (&prow)[D]) {
-                        const double* row = rec->P + lane * kPStride;
+  stream_row<S, Df2Cascade<true>>(xr, yr, tile, n, T, C, lane, p, clip,
+                                  zi ? zi + b * ld_state : nullptr, zf_row, 2 * stages, vec_x,
+                                  vec_y, [&](double (&prow)[D]) {
+                                    const double* row = rec->P + lane * kPStride;
 #pragma unroll
-                        for (int j = 0; j < D; ++j) prow[j] = row[j];
-                      });
+                                    for (int j = 0; j < D; ++j) prow[j] = row[j];
+                                  });
 }
 
 int bank_build(void* bank_host, size_t bank_bytes, const double* sos, const int32_t* stages,

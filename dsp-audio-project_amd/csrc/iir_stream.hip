@@ -53,12 +53,13 @@ __global__ __launch_bounds__(kWave) void k_iir_stream(const float* x, float* y, 
   __shared__ __attribute__((aligned(16))) float tile[kWave * kRow];
   const int lane = threadIdx.x;
   const int64_t b = blockIdx.x;
-  stream_row<S, NORM>(x + b * ld_x, y + b * ld_y, tile, n, T, C, lane, p, clip,
-                      zi ? zi + b * ld_state : nullptr, zf ? zf + b * ld_state : nullptr, Du,
-                      vec_x, vec_y, [&](double (&prow)[D]) {
+  stream_row<S, Df2Cascade<NORM>>(x + b * ld_x, y + b * ld_y, tile, n, T, C, lane, p, clip,
+                                  zi ? zi + b * ld_state : nullptr,
+                                  zf ? zf + b * ld_state : nullptr, Du, vec_x, vec_y,
+                                  [&](double (&prow)[D]) {
 #pragma unroll
-                        for (int j = 0; j < D; ++j) prow[j] = sp.P[lane * D + j];
-                      });
+                                    for (int j = 0; j < D; ++j) prow[j] = sp.P[lane * D + j];
+                                  });
 }
 
 // S == 0: y = x, clipped when asked.

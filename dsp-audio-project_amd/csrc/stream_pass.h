@@ -1,10 +1,13 @@
-// Device code shared by the streaming cascade (iir_stream.hip) and the EQ bank
-// (iir_bank.hip): one wavefront filters one channel's block of n samples, cut
-// into C <= 64 chunks of T samples (lane c = chunk c), from an entry state to
-// an exit state.  The two kernels differ only in where the coefficients and the
-// chunk transition A^T come from; the arithmetic below is the same
-// instructions in the same order for both, so a row's result is bitwise the
-// same through either.
+// Device code shared by the streaming cascade (iir_stream.hip), the EQ bank
+// (iir_bank.hip) and the live EQ (iir_live.hip): one wavefront filters one
+// channel's block of n samples, cut into C <= 64 chunks of T samples (lane c =
+// chunk c), from an entry state to an exit state.  The first two kernels differ
+// only in where the coefficients and the chunk transition A^T come from; the
+// arithmetic below is the same instructions in the same order for both, so a
+// row's result is bitwise the same through either.  The realisation -- what
+// the two state words of a stage mean and how one sample steps them -- is a
+// policy R: R::Params is what a pass reads, R::step<S>(u, s1, s2, p) one
+// sample through the S stages.
 #pragma once
 
 #include "cascade.h"
@@ -18,6 +21,18 @@ constexpr int kLoads = kTS / 4;  // 4-sample vectors per thread per tile
 constexpr int kMaxChunk = 2048;  // T = 32 ceil(n / 2048) gives C <= 64 up to n = 2^30
 
 __device__ __forceinline__ void wave_fence() { asm volatile("" ::: "memory"); }
+
+// The direct form II of cascade.h (iir_stream.hip, iir_bank.hip): s1, s2 are
+// the delay lines w1, w2.
+template <bool NORM>
+struct Df2Cascade {
+  using Params = SosParams;
+  template <int S>
+  static __device__ __forceinline__ double step(double u, double (&s1)[S], double (&s2)[S],
+                                                const Params& p) {
+    return cascade_step<S, NORM>(u, s1, s2, p);
+  }
+};
 
 // Tile [t0, t0 + 32) of the wave's 64 chunk rows: thread tid loads vector
 // (tid & 7) of rows i * 8 + (tid >> 3) (8 threads per row, 128 contiguous
@@ -87,11 +102,11 @@ __device__ __forceinline__ void tile_store(float* yr, const float* tile, int64_t
 // straight from the loop, under a wave-uniform test of the sample index, so
 // the exit state costs no registers in the tiles that do not hold it.  xr may
 // equal yr: a tile is read before it is written and tiles do not overlap.
-template <int S, bool NORM, bool APPLY>
+template <int S, class R, bool APPLY>
 __device__ __forceinline__ void stream_pass(const float* xr, float* yr, float* tile, int64_t n,
                                             int64_t T, int lane, double (&s1)[S], double (&s2)[S],
-                                            const SosParams& p, int clip, int vec_x, int vec_y,
-                                            int cap, double* zf, int Du) {
+                                            const typename R::Params& p, int clip, int vec_x,
+                                            int vec_y, int cap, double* zf, int Du) {
   float* my = tile + lane * kRow;
   float4 v[kLoads];
   fetch(v, xr, n, T, 0, lane, vec_x);
@@ -104,7 +119,7 @@ __device__ __forceinline__ void stream_pass(const float* xr, float* yr, float* t
     if constexpr (APPLY) {
 #pragma unroll 8
       for (int j = 0; j < kTS; ++j) {
-        const float out = (float)cascade_step<S, NORM>((double)my[j], s1, s2, p);
+        const float out = (float)R::template step<S>((double)my[j], s1, s2, p);
         my[j] = clip_f32(out, clo, chi);
         if (t0 + j + 1 == cap && zf) {  // the row's last sample: the exit state, unclipped
           double f[2 * S];
@@ -123,7 +138,7 @@ __device__ __forceinline__ void stream_pass(const float* xr, float* yr, float* t
       tile_store(yr, tile, n, T, t0, lane, vec_y);
     } else {
 #pragma unroll 8
-      for (int j = 0; j < kTS; ++j) (void)cascade_step<S, NORM>((double)my[j], s1, s2, p);
+      for (int j = 0; j < kTS; ++j) (void)R::template step<S>((double)my[j], s1, s2, p);
     }
   }
   wave_fence();
@@ -137,10 +152,11 @@ __device__ __forceinline__ void stream_pass(const float* xr, float* yr, float* t
 //   load_prow:  fills a lane's row of A^T (called by lanes below D = 2S).
 // Everything is wave-private: LDS instructions of one wave execute in program
 // order, so the tile hand-offs and the scan need compiler fences only.
-template <int S, bool NORM, class PROW>
+template <int S, class R, class PROW>
 __device__ __forceinline__ void stream_row(const float* xr, float* yr, float* tile, int64_t n,
-                                           int64_t T, int C, int lane, const SosParams& p,
-                                           int clip, const double* zi_row, double* zf_row, int Du,
+                                           int64_t T, int C, int lane,
+                                           const typename R::Params& p, int clip,
+                                           const double* zi_row, double* zf_row, int Du,
                                            int vec_x, int vec_y, PROW load_prow) {
   constexpr int D = 2 * S;
   static_assert(kWave * D * 2 <= kWave * kRow, "the scan must fit in the tile");
@@ -152,8 +168,8 @@ __device__ __forceinline__ void stream_row(const float* xr, float* yr, float* ti
 
   // ---- pass 1: end state from rest of every chunk (the last one's is unused)
   if (C > 1)
-    stream_pass<S, NORM, false>(xr, yr, tile, n, T, lane, s1, s2, p, clip, vec_x, vec_y, 0, nullptr,
-                                0);
+    stream_pass<S, R, false>(xr, yr, tile, n, T, lane, s1, s2, p, clip, vec_x, vec_y, 0, nullptr,
+                             0);
   double e[D];
 #pragma unroll
   for (int k = 0; k < S; ++k) {
@@ -203,7 +219,7 @@ __device__ __forceinline__ void stream_row(const float* xr, float* yr, float* ti
   // ---- pass 2: outputs from the carried states; lane C - 1 stores zf
   const int cap = (int)(n - (int64_t)(C - 1) * T);
   double* zo = (zf_row && lane == C - 1) ? zf_row : nullptr;
-  stream_pass<S, NORM, true>(xr, yr, tile, n, T, lane, s1, s2, p, clip, vec_x, vec_y, cap, zo, Du);
+  stream_pass<S, R, true>(xr, yr, tile, n, T, lane, s1, s2, p, clip, vec_x, vec_y, cap, zo, Du);
 }
 
 }  // namespace

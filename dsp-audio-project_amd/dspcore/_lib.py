@@ -38,8 +38,8 @@ _c_i32, _c_i64, _c_u64, _c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64,
 _vp, _dp = ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)
 
 # name -> (restype, argtypes); mirrors include/dspcore.h one to one, then
-# include/dspcore_stream.h and include/dspcore_eqbank.h.  load() requires every
-# one to be exported.
+# include/dspcore_stream.h, include/dspcore_eqbank.h and
+# include/dspcore_eqlive.h.  load() requires every one to be exported.
 _SIGNATURES = {
     "dsp_version": (ctypes.c_int, []),
     "dsp_last_error": (ctypes.c_char_p, []),
@@ -114,6 +114,13 @@ _SIGNATURES = {
     "dsp_eqbank_cascade_f32": (ctypes.c_int, [
         _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _c_sz, _c_i32, _c_i32, _c_i64, _vp, _vp,
         _vp, _c_i64, _vp]),
+    # include/dspcore_eqlive.h
+    "dsp_eqlive_version": (ctypes.c_int, []),
+    "dsp_eqlive_bytes": (_c_sz, [_c_i32]),
+    "dsp_eqlive_build": (ctypes.c_int, [_vp, _c_sz, _dp, _vp, _vp, _c_i32, _c_i32, _c_i64]),
+    "dsp_eqlive_cascade_f32": (ctypes.c_int, [
+        _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _c_sz, _c_i32, _c_i32, _c_i64, _vp, _vp,
+        _vp, _c_i64, _vp]),
 }
 STREAM_HEADER_PATH = os.path.join(REPO_ROOT, "include", "dspcore_stream.h")
 DSP_STREAM_MAX_STAGES = 8
@@ -121,6 +128,9 @@ DSP_STREAM_MAX_HIST = 4096
 EQBANK_HEADER_PATH = os.path.join(REPO_ROOT, "include", "dspcore_eqbank.h")
 DSP_EQBANK_MAX_STAGES = 8
 DSP_EQBANK_RECORD_BYTES = 2816
+EQLIVE_HEADER_PATH = os.path.join(REPO_ROOT, "include", "dspcore_eqlive.h")
+DSP_EQLIVE_MAX_SLOTS = 8
+DSP_EQLIVE_RECORD_BYTES = 2560
 DSP_TRACE_NAME = 32
 DSP_WAV_PCM = 1
 DSP_WAV_FLOAT = 3

@@ -233,6 +233,59 @@ def eq_plan(fs: float, gains: dict) -> EqPlan:
     return EqPlan(False, sos, tuple(centres))
 
 
+MAX_LIVE_SLOTS = 8       # include/dspcore_eqlive.h DSP_EQLIVE_MAX_SLOTS
+
+
+@dataclass(frozen=True)
+class LiveSlots:
+    """The fixed band slots of a live EQ (include/dspcore_eqlive.h): the keys
+    of the gains dict it was made with, in dict order."""
+    keys: tuple            # band names
+    fc: tuple              # centre of each slot after the clamp (dsp_core.py:240-246)
+    never: tuple           # fc <= 10 Hz: the reference never applies the band (:249)
+
+
+def live_slots(fs: float, keys) -> LiveSlots:
+    """Band slots for the names `keys` at the rate fs: fc from the centre table
+    (1000 Hz for an unknown name), clamped to 0.9 * fs / 2 when at or above it;
+    a slot with fc <= 10 Hz is never active."""
+    keys = tuple(keys)
+    if not 1 <= len(keys) <= MAX_LIVE_SLOTS:
+        raise ValueError(f"a live EQ takes 1 .. {MAX_LIVE_SLOTS} band slots (got {len(keys)})")
+    ceiling = (fs / 2.0) * NYQUIST_FRACTION
+    fcs = []
+    for name in keys:
+        fc = BAND_CENTRES_HZ.get(name, DEFAULT_CENTRE_HZ)
+        if fc >= ceiling:
+            fc = ceiling
+        fcs.append(fc)
+    return LiveSlots(keys, tuple(fcs), tuple(not fc > MIN_CENTRE_HZ for fc in fcs))
+
+
+def live_active(slots: LiveSlots, gains: dict) -> tuple:
+    """Which slots the reference would filter with for `gains` (|g| > 0.1 and
+    fc > 10 Hz).  `gains` must have exactly the slots' keys in their order."""
+    if tuple(gains.keys()) != slots.keys:
+        raise ValueError(f"a live EQ's gains must keep its band slots {list(slots.keys)} in "
+                         f"that order (got {list(gains.keys())})")
+    return tuple(abs(g) > BYPASS_DB and not nv for g, nv in zip(gains.values(), slots.never))
+
+
+def live_sos(fs: float, slots: LiveSlots, gains: dict) -> tuple[np.ndarray, bool]:
+    """(float64 [slots][5] = {b0 b1 b2 a1 a2}, clip) of one channel's block:
+    slot k is peaking_biquad(fc_k, fs, g) where live_active says so and the same
+    design at g = 0.0 otherwise, the flat section (b == a bitwise, b0 == 1.0:
+    it passes a signal at rest exactly and lets a ringing state ring out).  The
+    clip is the reference's: on unless every |g| < 0.1 (dsp_core.py:222, :254)."""
+    active = live_active(slots, gains)
+    rows = []
+    for fc, g, on in zip(slots.fc, gains.values(), active):
+        b, a = peaking_biquad(fc, fs, g if on else 0.0)
+        rows.append([b[0], b[1], b[2], a[1], a[2]])
+    clip = not all(abs(g) < BYPASS_DB for g in gains.values())
+    return np.asarray(rows, dtype=np.float64).reshape(-1, 5), clip
+
+
 def tf_to_sos_row(b, a) -> np.ndarray:
     """(b, a) of order <= 2 -> one normalised DF2T row {b0 b1 b2 a1 a2}.
 

@@ -23,6 +23,7 @@ from . import _lib, ops
 from .chain import ROW_ALIGN
 from .design import caller_taps, eq_plan, stream_src_plan
 from .eqbank import EqBank
+from .eqlive import LiveEq
 
 
 def _pitch(n: int) -> int:
@@ -41,20 +42,28 @@ class StreamChain:
     stream with the outputs whose windows reach past the last input; after it
     only reset() (or load_state_dict) makes the object usable again.
 
-    The EQ state belongs to the cascade it was filtered with: changing the
-    gains mid-stream would click, so a new plan means a new StreamChain (or
-    reset()).  With every |gain| < 0.1 the reference bypasses the EQ and z is
-    y (no clip, dsp_core.py:222-223).
+    The EQ state belongs to the cascade it was filtered with, so the gains of
+    such a chain are fixed; live=True (below) is the mode whose gains may
+    change mid-stream.  With every |gain| < 0.1 the reference bypasses the EQ
+    and z is y (no clip, dsp_core.py:222-223).
 
     `gains` is one dict for every channel, or a sequence of `batch` dicts, one
     per channel: the cascade is then an EqBank (dspcore.eqbank, one launch,
     `iir_bank`, in place of `iir_stream`) with max_n = the longest block the
     SRC can produce, the state tensor is [batch, 2 * (the largest stage
     count)], and a channel whose own plan is the bypass gets z = y in its
-    rows of the one z buffer."""
+    rows of the one z buffer.
+
+    live=True: the cascade is a LiveEq (dspcore.eqlive, one launch,
+    `iir_live`) with max_n = the longest block the SRC can produce.  The keys
+    of `gains` (one dict or `batch` dicts) are its band slots, every band
+    carries scipy's lfilter state, and set_gains(gains) changes the gains
+    between two blocks without a click: the new ones hold from the next push /
+    flush.  With live=False nothing differs from the above."""
 
     def __init__(self, fs: int, L: int, M: int, num_taps: int | None, gains, batch: int,
-                 max_block: int, device: torch.device | str = "cuda", keep_y: bool = True):
+                 max_block: int, device: torch.device | str = "cuda", keep_y: bool = True,
+                 live: bool = False):
         ops.require_gpu()
         self.B = int(batch)
         self.max_block = int(max_block)
@@ -86,7 +95,14 @@ class StreamChain:
             self._ldx = _pitch(self.hist + self.max_block + 1)
             self._xs = torch.zeros((self.B, self._ldx), dtype=torch.float32, device=dev)
             self._ybuf = torch.empty((self.B, _pitch(max_out)), dtype=torch.float32, device=dev)
-        self.bank = None
+        self.bank = self.live = None
+        if live:
+            self.eq = self.sos = None
+            self.live = LiveEq(self.fs_out, gains, max_out, dev, batch=self.B)
+            self._zbuf = torch.empty((self.B, _pitch(max_out)), dtype=torch.float32, device=dev)
+            self._state = self.live._state      # the LiveEq carries it in place
+            self.reset()
+            return
         if not isinstance(gains, dict):
             # one gains dict per channel: the EQ bank (dspcore.eqbank), whose
             # chunking is fixed by the longest block the SRC can hand it
@@ -114,9 +130,19 @@ class StreamChain:
         self.consumed = 0
         self.produced = 0
         self.flushed = False
-        self._state.zero_()
+        if self.live is not None:
+            self.live.reset()
+        else:
+            self._state.zero_()
         if not self.identity_src:
             self._xs.zero_()
+
+    def set_gains(self, gains) -> None:
+        """Live chains only: new gains (one dict, or one per channel, with the
+        band slots of the constructor's) from the next push / flush on."""
+        if self.live is None:
+            raise RuntimeError("set_gains needs a live chain: StreamChain(..., live=True)")
+        self.live.set_gains(gains)
 
     def state_dict(self) -> dict:
         """History, EQ state and counters (host copies), for checkpointing; a
@@ -124,8 +150,11 @@ class StreamChain:
         Synchronises the stream."""
         hist = (torch.empty((self.B, 0), dtype=torch.float32) if self.identity_src
                 else self._xs[:, :self.hist].cpu())
-        return {"history": hist, "eq_state": self._state.cpu(), "consumed": self.consumed,
-                "produced": self.produced, "flushed": self.flushed}
+        sd = {"history": hist, "eq_state": self._state.cpu(), "consumed": self.consumed,
+              "produced": self.produced, "flushed": self.flushed}
+        if self.live is not None:
+            sd["eq_active"] = self.live.state_dict()["ever_active"]
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
         hist, state = sd["history"], sd["eq_state"]
@@ -134,7 +163,10 @@ class StreamChain:
         self.reset()
         if self.hist:
             self._xs[:, :self.hist].copy_(hist)
-        self._state.copy_(state)
+        if self.live is not None:
+            self.live.load_state_dict({"zi": state, "ever_active": sd.get("eq_active")})
+        else:
+            self._state.copy_(state)
         self.consumed = int(sd["consumed"])
         self.produced = int(sd["produced"])
         self.flushed = bool(sd["flushed"])
@@ -151,6 +183,11 @@ class StreamChain:
         return c.value, n.value
 
     def _eq(self, y: torch.Tensor) -> torch.Tensor:
+        if self.live is not None:
+            z = self._zbuf[:, :y.shape[1]]
+            if y.shape[1]:
+                self.live.apply(y, out=z)
+            return z
         if self.bank is not None:
             z = self._zbuf[:, :y.shape[1]]
             if y.shape[1]:

@@ -94,7 +94,8 @@ int dsp_eqbank_build(void* bank_host, size_t bank_bytes, const double* sos_host,
  * w1_1, ...); the rest is neither read nor written.  zi == NULL starts from
  * rest; zf == NULL stores nothing; zi == zf (in place) and x == y are allowed.
  * The clip never touches the state.  A state is valid only for the group that
- * produced it.  Non-finite input and entry states behave as in
+ * produced it; gains that change mid-stream are the live EQ's
+ * (dspcore_eqlive.h).  Non-finite input and entry states behave as in
  * dsp_stream_cascade_f32.
  *
  * Bypass groups (stages[g] == 0): the row is copied, clipped only if clip[g],

@@ -55,13 +55,13 @@ int dsp_stream_version(void);
  *                            u = g w + c1 w1_k + c2 w2_k;  w2_k = w1_k; w1_k = w
  * with g = 1, c = (b1, b2) / b0, G = prod b0 when every b0 != 0, and g = b0,
  * c = (b1, b2), G = 1 otherwise (csrc/cascade.h, dspcore/design.py:
- * state_space).  It is NOT scipy's direct-form-II-transposed `zi`: the map
- * between the two is singular for a flat band (b == a), so there is no import
- * from lfilter states.  A state is valid only for the `sos` that produced it
- * (changing the coefficients mid-stream clicks; start the new cascade from
- * rest).  zi == NULL starts from rest; zf == NULL stores nothing; zi == zf (in
- * place) is allowed, and so is x == y.  Elements [2S, ld_state) of a state row
- * are neither read nor written.
+ * state_space).  It is NOT scipy's direct-form-II-transposed `zi`, and a state
+ * is valid only for the `sos` that produced it: start a new cascade from rest.
+ * Coefficients that change mid-stream, and states imported from or exported
+ * to lfilter, are the live EQ's (dspcore_eqlive.h), which carries lfilter's
+ * own state.  zi == NULL starts from rest; zf == NULL stores nothing; zi == zf
+ * (in place) is allowed, and so is x == y.  Elements [2S, ld_state) of a state
+ * row are neither read nor written.
  *
  * The clip (clip != 0: to [-1, 1]) applies to the output only; the state is
  * that of the unclipped recursion, as the reference clips once after the whole
