@@ -1669,3 +1669,155 @@ int launch_dft(const float* in, float* out, int64_t B, int64_t n, int real_in, i
 }
 
 }  // namespace dsp
+
+// ---------------------------------------------------------------------------
+// Streaming STFT magnitude (include/dspcore_stspec.h): the frames that one
+// push of a stream completes, and the carry the next push starts from, in one
+// launch.  It sits here for the pass code above (Plan, Tw, run_pass), which it
+// shares with k_spec_real; no kernel above depends on it.
+//
+// Transform workgroups (blockIdx.x < tgroups) are k_spec_real's scheme:
+// transform t = (row, frame) packs its N real samples as N/2 complex, pass 0
+// reads memory, the other passes run in LDS, the real split gives |X[k]|.
+// Only pass 0's loader differs: sample i of frame f is position f * hop + i of
+// the virtual row [carry_in[row][0:carry_len] | block[row][0:n_block]], zero
+// past its end (the flush's zero padding).  A pair that lies in one source at
+// an 8-byte aligned address is one float2 load, any other pair two guarded
+// scalar loads: the same values, so a frame's bits do not depend on how the
+// stream was cut into blocks.
+//
+// Carry workgroups (the remaining blockIdx.x) copy row[frames * hop + j],
+// j < carry_out_len, into carry_out, a buffer no workgroup of the launch
+// reads.  A push is a handful of frames per channel and launch-bound, so the
+// persistent prefetching kernels above (tuned for batches that fill the chip)
+// are not the model here.  Non-finite input is repaired by a second launch
+// (fft_nf.hip, two-source nf_input), as for dsp_stft_mag_f32.
+// ---------------------------------------------------------------------------
+namespace dsp {
+namespace {
+
+template <int NH>
+struct StreamSpecIO {
+  static constexpr bool kLdsIn = false;
+  const float* c;    // the frame's sample 0 in carry_in's row (valid for i < nc)
+  const float* b;    // the frame's sample 0 in block's row (valid for nc <= i < nv)
+  const float* win;
+  float2* buf;
+  int nc, nv;        // samples of the frame in the carry / in the row, 0 <= nc <= nv <= N
+  bool live, pc, pb, pw;  // 8-byte alignment of c, b and win
+  __device__ __forceinline__ float sample(int i) const {
+    return i < nc ? c[i] : (i < nv ? b[i] : 0.f);
+  }
+  __device__ __forceinline__ float2 load(int n) const {
+    if (!live) return make_float2(0.f, 0.f);
+    const int i = 2 * n;
+    float2 sv;
+    if (pc && i + 1 < nc) {
+      sv = *reinterpret_cast<const float2*>(c + i);
+    } else if (pb && i >= nc && i + 1 < nv) {
+      sv = *reinterpret_cast<const float2*>(b + i);
+    } else {
+      sv = make_float2(sample(i), sample(i + 1));
+    }
+    const float2 wv = pw ? reinterpret_cast<const float2*>(win)[n] : make_float2(win[i], win[i + 1]);
+    return make_float2(sv.x * wv.x, sv.y * wv.y);
+  }
+  __device__ __forceinline__ void store(int k, float2 v) const { buf[lpad(k)] = v; }
+};
+
+template <int LOG2N>  // LOG2N of the real length N
+__global__ __launch_bounds__(Plan<LOG2N - 1>::NT) void k_stft_stream(StspecArgs a,
+                                                                      unsigned tgroups) {
+  using PL = Plan<LOG2N - 1>;
+  constexpr int N = 1 << LOG2N, NH = N / 2;
+  extern __shared__ __attribute__((aligned(16))) float2 lds[];
+  if (blockIdx.x >= tgroups) {
+    // carry update: element e = (row, j) of carry_out from the virtual row
+    const int64_t total = a.B * a.carry_out_len;
+    const int64_t start = a.frames * a.hop;
+    const int64_t step = (int64_t)(gridDim.x - tgroups) * PL::NT;
+    for (int64_t e = (int64_t)(blockIdx.x - tgroups) * PL::NT + threadIdx.x; e < total; e += step) {
+      const int64_t row = e / a.carry_out_len, j = e - row * a.carry_out_len;
+      const int64_t p = start + j;
+      a.carry_out[row * a.ld_carry + j] = p < a.carry_len
+                                              ? a.carry_in[row * a.ld_carry + p]
+                                              : a.block[row * a.ld_block + (p - a.carry_len)];
+    }
+    return;
+  }
+  const int tl = threadIdx.x / PL::TPT;
+  const int j0 = threadIdx.x - tl * PL::TPT;
+  const int64_t t = (int64_t)blockIdx.x * PL::TPB + tl;
+  const bool live = t < a.B * a.frames;
+  float2* buf = lds + tl * PL::PADN;
+  const float2* twt = reinterpret_cast<const float2*>(a.tw);
+  Tw<LOG2N - 1, 0> tw;
+  load_tw<LOG2N - 1, 0>(tw, twt, j0, 2);
+  const int64_t tt = live ? t : 0;
+  const int64_t row = a.frames == 1 ? tt : tt / a.frames;
+  const int64_t f0 = (tt - row * a.frames) * a.hop;  // the frame's start in the virtual row
+  const int64_t ncl = a.carry_len - f0, nvl = a.carry_len + a.n_block - f0;
+  const int nc = (int)(ncl < 0 ? 0 : (ncl > N ? N : ncl));
+  const int nv = (int)(nvl < nc ? nc : (nvl > N ? N : nvl));
+  // (pointers to the frame's sample 0 in either source; each is dereferenced
+  // only at the indices that lie inside its source)
+  const float* c = a.carry_in + (row * a.ld_carry + f0);
+  const float* b = a.block + (row * a.ld_block + (f0 - a.carry_len));
+  const StreamSpecIO<NH> io{c, b, a.win, buf, nc, nv, live,
+                            (reinterpret_cast<uintptr_t>(c) & 7) == 0,
+                            (reinterpret_cast<uintptr_t>(b) & 7) == 0,
+                            (reinterpret_cast<uintptr_t>(a.win) & 7) == 0};
+  run_pass<LOG2N - 1, 0>(io, buf, j0, tw);
+  __syncthreads();  // the last pass stored Z into LDS
+  if (!live) return;
+  float* mr = a.mag + t * a.ld_mag;
+  for (int k = j0; k <= NH / 2; k += PL::TPT) {  // the real split of k_spec_real
+    const float2 zk = buf[lpad(k)];
+    const float2 zm = buf[lpad((NH - k) & (NH - 1))];
+    const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
+    const float2 o = make_float2(0.5f * (zk.y + zm.y), -0.5f * (zk.x - zm.x));
+    const float2 w = twt[k < NH ? k : 0];
+    const float2 wo = cmulv(o, w);
+    const float2 xk = cadd(e, wo), xm = csub(e, wo);
+    mr[k] = cabsf_(xk);
+    if (k > 0 && k < NH / 2) mr[NH - k] = cabsf_(xm);
+    if (k == 0) mr[NH] = fabsf(zk.x - zk.y);
+  }
+}
+
+constexpr int64_t kStspecCarryGroups = 1024;  // at most; the copy is grid-strided
+
+template <int LOG2N>
+int launch_stft_stream_n(const StspecArgs& a, hipStream_t s) {
+  using PL = Plan<LOG2N - 1>;
+  const size_t shm = (size_t)PL::TPB * PL::PADN * sizeof(float2);
+  if (int rc = allow_lds(k_stft_stream<LOG2N>, shm)) return rc;
+  const int64_t tg = ceil_div(a.B * a.frames, PL::TPB);
+  int64_t cg = ceil_div(a.B * a.carry_out_len, 4 * PL::NT);
+  cg = cg < 1 ? 1 : (cg > kStspecCarryGroups ? kStspecCarryGroups : cg);
+  DSP_REQUIRE(tg + cg <= INT32_MAX, "too many frames in one call");
+  hipLaunchKernelGGL(k_stft_stream<LOG2N>, dim3((unsigned)(tg + cg)), dim3(PL::NT), shm, s, a,
+                     (unsigned)tg);
+  DSP_LAUNCHED("k_stft_stream");
+  return DSP_OK;
+}
+
+}  // namespace
+
+int launch_stft_stream(const StspecArgs& a, int log2n, hipStream_t s) {
+  switch (log2n) {
+    case 5: return launch_stft_stream_n<5>(a, s);
+    case 6: return launch_stft_stream_n<6>(a, s);
+    case 7: return launch_stft_stream_n<7>(a, s);
+    case 8: return launch_stft_stream_n<8>(a, s);
+    case 9: return launch_stft_stream_n<9>(a, s);
+    case 10: return launch_stft_stream_n<10>(a, s);
+    case 11: return launch_stft_stream_n<11>(a, s);
+    case 12: return launch_stft_stream_n<12>(a, s);
+    case 13: return launch_stft_stream_n<13>(a, s);
+    case 14: return launch_stft_stream_n<14>(a, s);
+    default: return set_error(DSP_ENOTSUP, "log2n=%d outside [5, 14]", log2n);
+  }
+}
+
+}  // namespace dsp

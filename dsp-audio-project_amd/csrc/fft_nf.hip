@@ -63,6 +63,12 @@ __device__ __forceinline__ float2 nf_input(const NfArgs& a, int64_t t, int64_t n
   if (a.mode == 2) {
     const int64_t row = a.frames == 1 ? t : t / a.frames;
     const int64_t f0 = (t - row * a.frames) * a.hop;
+    if (a.in2) {  // two-source rows: [in[0:split] | in2[0:seg_len - split]]
+      const int64_t p = f0 + n;
+      const float s = p < a.split ? a.in[row * a.ld_in + p]
+                                  : (p < a.seg_len ? a.in2[row * a.ld_in2 + (p - a.split)] : 0.f);
+      return make_float2(s * a.win[n], 0.f);
+    }
     const float s = (n < a.seg_len - f0) ? a.in[row * a.ld_in + a.seg_start + f0 + n] : 0.f;
     return make_float2(s * a.win[n], 0.f);
   }

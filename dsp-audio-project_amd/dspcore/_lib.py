@@ -38,8 +38,9 @@ _c_i32, _c_i64, _c_u64, _c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64,
 _vp, _dp = ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)
 
 # name -> (restype, argtypes); mirrors include/dspcore.h one to one, then
-# include/dspcore_stream.h, include/dspcore_eqbank.h and
-# include/dspcore_eqlive.h.  load() requires every one to be exported.
+# include/dspcore_stream.h, include/dspcore_eqbank.h,
+# include/dspcore_eqlive.h and include/dspcore_stspec.h.  load() requires
+# every one to be exported.
 _SIGNATURES = {
     "dsp_version": (ctypes.c_int, []),
     "dsp_last_error": (ctypes.c_char_p, []),
@@ -121,6 +122,14 @@ _SIGNATURES = {
     "dsp_eqlive_cascade_f32": (ctypes.c_int, [
         _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _c_sz, _c_i32, _c_i32, _c_i64, _vp, _vp,
         _vp, _c_i64, _vp]),
+    # include/dspcore_stspec.h
+    "dsp_stspec_version": (ctypes.c_int, []),
+    "dsp_stspec_geometry": (ctypes.c_int, [
+        _c_i32, _c_i64, _c_i64, _c_i64, _c_i32, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64),
+        ctypes.POINTER(_c_i64)]),
+    "dsp_stspec_mag_f32": (ctypes.c_int, [
+        _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _vp, _c_i64, _c_i64, _c_i32, _c_i64, _c_i64,
+        _c_i32, _vp, _vp, _vp]),
 }
 STREAM_HEADER_PATH = os.path.join(REPO_ROOT, "include", "dspcore_stream.h")
 DSP_STREAM_MAX_STAGES = 8
@@ -131,6 +140,8 @@ DSP_EQBANK_RECORD_BYTES = 2816
 EQLIVE_HEADER_PATH = os.path.join(REPO_ROOT, "include", "dspcore_eqlive.h")
 DSP_EQLIVE_MAX_SLOTS = 8
 DSP_EQLIVE_RECORD_BYTES = 2560
+STSPEC_HEADER_PATH = os.path.join(REPO_ROOT, "include", "dspcore_stspec.h")
+DSP_STSPEC_MIN_LOG2N = 5
 DSP_TRACE_NAME = 32
 DSP_WAV_PCM = 1
 DSP_WAV_FLOAT = 3

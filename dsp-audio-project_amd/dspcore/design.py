@@ -568,6 +568,46 @@ def stft_plan(length: int, n_fft: int = SPECTRUM_WINDOW, hop: int | None = None)
     return StftPlan(n_fft, hop, frames)
 
 
+@dataclass(frozen=True)
+class StreamStftPlan:
+    """One call of the stream spectrum (include/dspcore_stspec.h): the samples
+    carried into it, the frames it emits and the samples it carries out."""
+    carry_len: int
+    frames: int
+    carry_out_len: int
+
+
+def stream_stft_plan(n_fft: int, hop: int | None, seen: int, n_block: int,
+                     flush: bool = False) -> StreamStftPlan:
+    """stft_plan's framing for a stream cut into blocks: after `seen` samples,
+    F(seen) = 0 for seen < n_fft, else 1 + (seen - n_fft) // hop frames are
+    complete and seen - F(seen) hop (< n_fft) samples are carried.  A block of
+    n_block samples emits frames F(seen) .. F(seen + n_block) - 1; the flush
+    (n_block == 0) emits the zero-padded frame that stft_plan(seen) still owes
+    (0 or 1) and carries nothing out.  The frames of all calls of a stream of
+    `total` samples, flush included, are stft_plan(total).frames."""
+    n_fft, seen, n_block = int(n_fft), int(seen), int(n_block)
+    if n_fft < 1 or n_fft & (n_fft - 1):
+        raise ValueError(f"n_fft={n_fft} is not a power of two; the radix-2 FFT needs 2^k points")
+    hop = max(1, n_fft // 4) if hop is None else int(hop)
+    if hop < 1 or hop > n_fft:
+        raise ValueError(f"hop={hop} outside [1, n_fft={n_fft}]")
+    if seen < 0 or n_block < 0:
+        raise ValueError("seen and n_block must be >= 0")
+    if flush and n_block:
+        raise ValueError("a flush takes no block")
+
+    def complete(s: int) -> int:
+        return 0 if s < n_fft else 1 + (s - n_fft) // hop
+
+    done = complete(seen)
+    carry = seen - done * hop
+    if flush:
+        return StreamStftPlan(carry, stft_plan(seen, n_fft, hop).frames - done, 0)
+    frames = complete(seen + n_block) - done
+    return StreamStftPlan(carry, frames, carry + n_block - frames * hop)
+
+
 def hann(n: int) -> np.ndarray:
     """Window of dsp_core.py:85-87: 0.5 - 0.5 cos(2 pi n / (N - 1)), float64."""
     k = np.arange(n)

@@ -24,6 +24,7 @@ from .chain import ROW_ALIGN
 from .design import caller_taps, eq_plan, stream_src_plan
 from .eqbank import EqBank
 from .eqlive import LiveEq
+from .stspec import StreamSpectrum
 
 
 def _pitch(n: int) -> int:
@@ -59,11 +60,19 @@ class StreamChain:
     of `gains` (one dict or `batch` dicts) are its band slots, every band
     carries scipy's lfilter state, and set_gains(gains) changes the gains
     between two blocks without a click: the new ones hold from the next push /
-    flush.  With live=False nothing differs from the above."""
+    flush.  With live=False nothing differs from the above.
+
+    spectrum=dict(n_fft=..., hop=...) adds a running spectrogram of z
+    (dspcore.stspec.StreamSpectrum, two more launches per push: `stspec`,
+    `stspec_nf`): push and flush then return (y, z, mag), mag [batch, frames,
+    n_fft/2 + 1] the STFT frames of z that the block completed (flush: those of
+    its last outputs, then the zero-padded frame design.stft_plan still owes),
+    valid until the next call.  With spectrum=None nothing differs from the
+    above."""
 
     def __init__(self, fs: int, L: int, M: int, num_taps: int | None, gains, batch: int,
                  max_block: int, device: torch.device | str = "cuda", keep_y: bool = True,
-                 live: bool = False):
+                 live: bool = False, spectrum: dict | None = None):
         ops.require_gpu()
         self.B = int(batch)
         self.max_block = int(max_block)
@@ -95,6 +104,9 @@ class StreamChain:
             self._ldx = _pitch(self.hist + self.max_block + 1)
             self._xs = torch.zeros((self.B, self._ldx), dtype=torch.float32, device=dev)
             self._ybuf = torch.empty((self.B, _pitch(max_out)), dtype=torch.float32, device=dev)
+        # the spectrum of z: its longest block is the longest the SRC can produce
+        self.spec = (None if spectrum is None else
+                     StreamSpectrum(batch=self.B, max_block=max_out, device=dev, **spectrum))
         self.bank = self.live = None
         if live:
             self.eq = self.sos = None
@@ -136,6 +148,8 @@ class StreamChain:
             self._state.zero_()
         if not self.identity_src:
             self._xs.zero_()
+        if self.spec is not None:
+            self.spec.reset()
 
     def set_gains(self, gains) -> None:
         """Live chains only: new gains (one dict, or one per channel, with the
@@ -154,6 +168,8 @@ class StreamChain:
               "produced": self.produced, "flushed": self.flushed}
         if self.live is not None:
             sd["eq_active"] = self.live.state_dict()["ever_active"]
+        if self.spec is not None:
+            sd["spectrum"] = self.spec.state_dict()
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -170,6 +186,10 @@ class StreamChain:
         self.consumed = int(sd["consumed"])
         self.produced = int(sd["produced"])
         self.flushed = bool(sd["flushed"])
+        if self.spec is not None:
+            if "spectrum" not in sd:
+                raise ValueError("state_dict is of a chain without a spectrum")
+            self.spec.load_state_dict(sd["spectrum"])
 
     # -- one block ---------------------------------------------------------------
     def _geometry(self, n_block: int, flush: bool) -> tuple[int, int]:
@@ -213,6 +233,17 @@ class StreamChain:
             _lib.check(rc, "dsp_src_polyphase_f32")
         return y
 
+    def _out(self, y: torch.Tensor, z: torch.Tensor, last: bool = False):
+        """What push / flush return: (y, z), and the frames of z with a spectrum."""
+        y = y if self.keep_y else None
+        if self.spec is None:
+            return y, z
+        mag = self.spec.push(z)
+        if last:   # the frames of the last outputs, then the frame the plan still owes
+            mag = mag.clone()   # (the flush reuses the buffer that `mag` is a view of)
+            mag = torch.cat([mag, self.spec.flush()], dim=1)
+        return y, z, mag
+
     def push(self, x_block: torch.Tensor):
         if self.flushed:
             raise RuntimeError("the stream was flushed; reset() starts a new one")
@@ -226,7 +257,7 @@ class StreamChain:
             z = self._eq(y)
             self.consumed += n
             self.produced += n
-            return (y if self.keep_y else None), z
+            return self._out(y, z)
         c_offset, n_out = self._geometry(n, False)
         self._xs[:, self.hist:self.hist + n].copy_(x_block)
         y = self._src(self.hist + n, c_offset, n_out)
@@ -238,7 +269,7 @@ class StreamChain:
         _lib.check(rc, "dsp_stream_roll_f32")
         self.consumed += n
         self.produced += n_out
-        return (y if self.keep_y else None), z
+        return self._out(y, z)
 
     def flush(self):
         """Ends the stream: the last ceil(consumed L / M) - produced outputs."""
@@ -247,7 +278,7 @@ class StreamChain:
         self.flushed = True
         if self.identity_src:
             y = torch.empty((self.B, 0), dtype=torch.float32, device=self.device)
-            return (y if self.keep_y else None), y
+            return self._out(y, y, last=True)
         c_offset, n_out = self._geometry(0, True)
         n_in = self.hist
         if n_in == 0:   # K <= L: no history; the outputs left see zeros only
@@ -256,4 +287,4 @@ class StreamChain:
         y = self._src(n_in, c_offset, n_out)
         z = self._eq(y)
         self.produced += n_out
-        return (y if self.keep_y else None), z
+        return self._out(y, z, last=True)

@@ -13,6 +13,18 @@ fails or runs out of time ends the run: nothing more is started.
 
 Writes one JSON document: the device name and one record per step with ms per
 push and input samples/s of the stream, and samples/s of the one-shot chain.
+
+    python tools/stream_bench.py --spectrum [--out profiles/stream_spectrum_bench.json]
+
+times, on the same four shapes, what a running spectrogram of z (n_fft 4096,
+hop 1024) costs a push, three variants alternating in one process, the whole
+sequence twice (the difference between the two rounds is the spread):
+  plain     StreamChain without a spectrum;
+  fused     StreamChain(..., spectrum=dict(n_fft=4096, hop=1024)): the frames and
+            the carry update in one launch, then the repair launch;
+  composed  the same from the one-shot entry points: a copy of z behind the
+            carried tail of a staging row, ops.stft_magnitude (two launches) over
+            the row, a copy of the new tail into the other staging buffer.
 """
 from __future__ import annotations
 
@@ -87,22 +99,94 @@ def one_step(block: int, batch: int) -> dict:
     }
 
 
+SPEC_N_FFT, SPEC_HOP = 4096, 1024
+
+
+def spectrum_step(block: int, batch: int) -> dict:
+    import torch
+
+    from dspcore import design, ops
+    from dspcore.stream import StreamChain
+    from oracle import dsp_ref_cpu as orc
+
+    dev = torch.device("cuda", 0)
+    gains = orc.CONFIG3_GAINS
+    gen = torch.Generator(device=dev).manual_seed(5)
+    xb = torch.rand((batch, block), device=dev, generator=gen) * 2 - 1
+    plain = StreamChain(FS, L, M, None, gains, batch, block, dev)
+    fused = StreamChain(FS, L, M, None, gains, batch, block, dev,
+                        spectrum=dict(n_fft=SPEC_N_FFT, hop=SPEC_HOP))
+    comp = StreamChain(FS, L, M, None, gains, batch, block, dev)
+    max_out = fused.spec.max_block
+    ld = -(-(SPEC_N_FFT + max_out) // 32) * 32
+    stage = [torch.zeros((batch, ld), dtype=torch.float32, device=dev) for _ in range(2)]
+    half = SPEC_N_FFT // 2 + 1
+    mag = torch.empty(batch * fused.spec.max_frames * half, dtype=torch.float32, device=dev)
+    st = {"cur": 0, "seen": 0}
+
+    def composed_push():
+        _, z = comp.push(xb)
+        n = z.shape[1]
+        p = design.stream_stft_plan(SPEC_N_FFT, SPEC_HOP, st["seen"], n)
+        row = stage[st["cur"]]
+        row[:, p.carry_len:p.carry_len + n].copy_(z)
+        if p.frames:   # (the samples its complete frames span: a lone frame takes n_fft at most)
+            span = (p.frames - 1) * SPEC_HOP + SPEC_N_FFT
+            ops.stft_magnitude(row[:, :span], SPEC_N_FFT, SPEC_HOP, p.frames,
+                               out=mag[:batch * p.frames * half].view(batch, p.frames, half))
+        stage[1 - st["cur"]][:, :p.carry_out_len].copy_(
+            row[:, p.frames * SPEC_HOP:p.carry_len + n])
+        st["cur"] = 1 - st["cur"]
+        st["seen"] += n
+
+    variants = (("plain", lambda: plain.push(xb)), ("fused", lambda: fused.push(xb)),
+                ("composed", composed_push))
+    rounds = []
+    for _ in range(2):
+        ms = {}
+        for name, push in variants:
+            for _ in range(WARMUP):
+                push()
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            for _ in range(PUSHES):
+                push()
+            torch.cuda.synchronize(dev)
+            ms[name] = (time.perf_counter() - t0) * 1e3 / PUSHES
+        rounds.append(ms)
+    rec = {"block": block, "batch": batch, "pushes": PUSHES, "n_fft": SPEC_N_FFT, "hop": SPEC_HOP,
+           "device": torch.cuda.get_device_name(dev)}
+    for name, _ in variants:
+        a, b = rounds[0][name], rounds[1][name]
+        rec[f"{name}_ms_per_push"] = [a, b]
+        rec[f"{name}_spread_ms"] = abs(a - b)
+    return rec
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_bench.json"))
+    ap.add_argument("--out", default=None,
+                    help="default profiles/stream_bench.json (stream_spectrum_bench.json with "
+                         "--spectrum)")
+    ap.add_argument("--spectrum", action="store_true",
+                    help="time a push without a spectrum, with the fused one and with the "
+                         "composition of the one-shot entry points")
     ap.add_argument("--one", nargs=2, type=int, metavar=("BLOCK", "BATCH"),
                     help="run one step in this process and print its record")
     args = ap.parse_args()
     if args.one:
-        print(json.dumps(one_step(*args.one)))
+        print(json.dumps((spectrum_step if args.spectrum else one_step)(*args.one)))
         return 0
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "stream_spectrum_bench.json" if args.spectrum
+                                else "stream_bench.json")
     steps = []
     for batch in BATCHES:
         for block in BLOCKS:
             try:
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", str(block),
-                                    str(batch)], capture_output=True, text=True,
-                                   timeout=STEP_TIMEOUT_S)
+                                    str(batch)] + (["--spectrum"] if args.spectrum else []),
+                                   capture_output=True, text=True, timeout=STEP_TIMEOUT_S)
             except subprocess.TimeoutExpired:
                 print(f"step block={block} batch={batch} ran out of time; stopping",
                       file=sys.stderr)
@@ -115,8 +199,10 @@ def main() -> int:
             rec = json.loads(r.stdout.strip().splitlines()[-1])
             steps.append(rec)
             print(json.dumps(rec), flush=True)
+    what = (f"; spectrum of z n_fft {SPEC_N_FFT} hop {SPEC_HOP}, three variants alternating, "
+            "two rounds" if args.spectrum else "")
     doc = {"workload": f"SRC {L}/{M} at {FS} Hz + 6-band EQ (config 3 gains), "
-                       f"{PUSHES} pushes per step after {WARMUP} warm-up pushes",
+                       f"{PUSHES} pushes per step after {WARMUP} warm-up pushes{what}",
            "device": steps[0].pop("device"), "steps": steps}
     for s in steps[1:]:
         s.pop("device", None)
