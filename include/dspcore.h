@@ -85,8 +85,10 @@ int dsp_src_polyphase_f32(const float* x, float* y, int64_t B, int64_t n_in,
  * The time axis is cut into chunks of `chunk_len` samples (multiple of 32)
  * whose initial states are recovered by a linear-recurrence carry scan, so
  * results do not depend on B or on how a batch is sharded.  x may equal y.
- * With S <= 8 (S != 7) and ceil(n / chunk_len) <= 64 the whole cascade is one
- * launch and needs no workspace.  `state_table` (optional, device, may be
+ * With S <= 8 and 2 <= ceil(n / chunk_len) <= 256 the whole cascade is one
+ * launch (S == 7 runs as 8 stages) and needs no workspace, and neither does a
+ * row of one chunk; dsp_biquad_workspace_bytes answers 0 for exactly these.
+ * `state_table` (optional, device, may be
  * NULL) is float64 [chunk_len][2S]: row t = A^(chunk_len-1-t) B, the state
  * response of the S-stage cascade (state order s1_0, s2_0, s1_1, ...) to a
  * unit sample t samples into a chunk; with it the chunk end states cost 2S
@@ -316,7 +318,7 @@ int dsp_stft_mag_f32(const float* x, float* mag, int64_t B, int64_t ld_x,
  * dsp_chain_xstate_geometry and row j = sum_t G[t] (L h)[t*M + c_offset -
  * (q0 + j)*L] composes the state-response table G of chunk_len (see
  * dsp_biquad_cascade_f32) with the float64 taps.  It needs 1 <= S <= 8,
- * S != 7, ceil(n_out / chunk_len) <= 64, chunk_len a multiple of 32,
+ * S != 7, 2 <= ceil(n_out / chunk_len) <= 256, chunk_len a multiple of 32,
  * chunk_len*M/L an integer multiple of 4 and 16-byte aligned rows of x.
  * Otherwise `state_table` (G, may be NULL) is used as in
  * dsp_biquad_cascade_f32.
