@@ -280,24 +280,6 @@ int launch_nf_small(const NfArgs& a, hipStream_t s);
 // at lists + r * list_stride 64-bit entries, >= N entries each).
 int launch_nf_large(const NfArgs& a, uint32_t* hdr, uint64_t* lists, int64_t list_stride,
                     hipStream_t s);
-// Streaming STFT magnitude (include/dspcore_stspec.h): the frames of one push
-// and the carry update in one launch (k_stft_stream, at the end of fft.hip
-// beside the pass code it shares).  A row is the virtual concatenation
-// [carry_in[row][0:carry_len] | block[row][0:n_block]], zero past its end;
-// frame f starts at f * hop; carry_out[row][j] = row[frames * hop + j] for
-// j < carry_out_len.  The entry point (stft_stream.hip) has checked everything.
-struct StspecArgs {
-  const float* carry_in;
-  float* carry_out;
-  const float* block;
-  float* mag;
-  int64_t ld_carry, ld_block, ld_mag;
-  int64_t B, frames, hop;
-  int64_t carry_len, n_block, carry_out_len;
-  const float* win;
-  const float* tw;
-};
-int launch_stft_stream(const StspecArgs& a, int log2n, hipStream_t s);
 size_t biquad_workspace_bytes(int64_t B, int64_t n, int S, int64_t chunk_len);
 // lfilter's non-finite labels after the cascade (lfilter_nf.hip).
 int launch_lfilter_nf(const float* x, float* y, int64_t B, int64_t n, int64_t ld_x, int64_t ld_y,

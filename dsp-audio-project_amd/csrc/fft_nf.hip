@@ -9,7 +9,7 @@
 // NaN wherever an infinite component meets the exactly-zero imaginary part of
 // W at k = 0, and the spectrum's |X| (:91) is hypot: +inf when either
 // component is infinite, NaN when one is NaN and none infinite.  The radix-16
-// Stockham kernels (fft.hip) compute the same finite numbers in another
+// Stockham kernels (fft_pass.h) compute the same finite numbers in another
 // order, so their inf / NaN labels differ.  What is restored here:
 //
 //   * the class (finite / +inf / -inf / NaN) of every output component is the

@@ -1,11 +1,13 @@
-"""Every in-LDS FFT, spectrum and any-length-DFT kernel of csrc/fft.hip at its
+"""Every in-LDS FFT, spectrum and any-length-DFT kernel of csrc/fft.hip,
+fft_spec.hip and fft_dft.hip (and fft_large.hip's two-launch four-step) at its
 edges: all 15 sizes of both complex modes, the spectrum and the STFT at
 n_fft = 2^1..2^14, every Bluestein size M = 2^1..2^14, and the two-launch
 four-step sizes that had not run in spectrum or real-input mode.
 
 Up to 2^14 points the dispatch tables pick one of ~75 template instantiations
-(k_fft<0..14, C2C | R2C | Spec>, k_spec_real<5, 9, 13>, k_spec_stream<6, 7, 8,
-10, 11, 14>, k_spec_wave12, k_bluestein<1..14>), each with its own Plan (first
+(fft.hip: k_fft<0..14, C2C | R2C> and <0..4, Spec>, k_spec_real<5, 9, 13>;
+fft_spec.hip: k_spec_stream<6, 7, 8, 10, 11, 14>, k_spec_wave12; fft_dft.hip:
+k_bluestein<1..14>), each with its own Plan (first
 radix, threads per transform TPT, transforms per workgroup TPB, padded LDS
 image).  The other modules reach them at a few sizes, with B <= 3 and a Hann
 window whose vanishing ends hide the first and last samples of every frame.
@@ -33,10 +35,10 @@ Method, for every part:
     sample; a frame with no valid sample must give exact zeros.
 
 The trace records scope names only (fft, fft_nf, spectrum, spectrum_nf, stft,
-dft); SPEC_ROUTE and TPB_OF below restate csrc/fft.hip's dispatch as literals
-and say which kernel a case is for.  k_spec_real<6, 7, 8, 10, 11, 12, 14> are
-unreachable by the default dispatch (dispatch_spec takes the streaming and
-one-wave kernels first) and are not run.
+dft); SPEC_ROUTE and TPB_OF below restate csrc/fft.hip's dispatch_spec and
+csrc/fft_pass.h's Plan as literals and say which kernel a case is for.  The
+spectrum has no other instantiation: k_spec_real<6, 7, 8, 10, 11, 12, 14> and
+k_fft<5..14, Spec>, which no size was ever routed to, are no longer compiled.
 
 Every case prints its worst error / bound ratio.
 """
@@ -53,7 +55,7 @@ IN_PAD = 1.0e3            # input padding: finite and far outside [-1, 1]
 SENT = -889262067         # output padding: the bits 0xCAFEF00D (a finite float)
 AMP = 0.75
 
-# csrc/fft.hip Plan (lines 197-198): TPT = N / RMAX, RMAX = 16 from N = 16 up;
+# csrc/fft_pass.h Plan (TPT, TPB): TPT = N / RMAX, RMAX = 16 from N = 16 up;
 # TPB = 256 / TPT, 1 from TPT = 256 up.
 TPB_OF = (256, 256, 256, 256, 256, 128, 64, 32, 16, 8, 4, 2, 1, 1, 1)
 
@@ -66,7 +68,7 @@ def TPB(k):
     return max(1, 256 // TPT(k))
 
 
-# csrc/fft.hip dispatch_spec (lines 1318-1342): log2n -> (kernel, Plan index /
+# csrc/fft.hip dispatch_spec: log2n -> (kernel, Plan index /
 # transforms per unit / waves per group).
 SPEC_ROUTE = {
     1: ("k_fft", 1), 2: ("k_fft", 2), 3: ("k_fft", 3), 4: ("k_fft", 4),

@@ -979,7 +979,7 @@ def _tones(n, f, amp, gpu, real=False):
 
 
 def test_fft_nested_four_step(gpu):
-    """2^29 and 2^30 (round 5, the nested four-step of csrc/fft.hip run_fft6_row;
+    """2^29 and 2^30 (round 5, the nested four-step of csrc/fft_large.hip run_fft6_row;
     the reference's recursion has no size cap, dsp_core.py:41-66): sums of
     tones against their exact DFT (max|dX| <= 1e-5 * max|X|), two complex rows
     at 2^29 and a real row at 2^30; the 2^29 spectrum against |FFT| of the same

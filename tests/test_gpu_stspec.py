@@ -1,4 +1,4 @@
-"""The stream spectrum on the GPU (include/dspcore_stspec.h, csrc/fft.hip
+"""The stream spectrum on the GPU (include/dspcore_stspec.h, csrc/stft_stream.hip
 k_stft_stream, dspcore.stspec.StreamSpectrum), through the C ABI and the class.
 
 Sizes N = 32, 512, 4096, 16384: Plan<log2 N - 1> packs 256, 16, 2 and 1
@@ -29,7 +29,7 @@ from test_gpu_parity import CHAIN_MAG_RTOL, FFT_RTOL, _traced
 pytestmark = pytest.mark.gpu
 
 SIZES = (32, 512, 4096, 16384)
-TPB = {32: 256, 512: 16, 4096: 2, 16384: 1}     # csrc/fft.hip Plan<log2 N - 1>::TPB
+TPB = {32: 256, 512: 16, 4096: 2, 16384: 1}     # csrc/fft_pass.h Plan<log2 N - 1>::TPB
 
 
 def _hop(N):

@@ -6,7 +6,7 @@ kernel walks channel groups grid-stride with the next channel's window in
 flight (csrc/chain_tile.hip, k_chain_gcp), the repair kernels take 64 channels
 per wave on a grid capped at 1024 workgroups (csrc/chain_tile.h,
 repair_channels), the spectrum / STFT kernel is a persistent grid of two
-transforms per workgroup (csrc/fft.hip, k_spec_stream), the SRC launches in
+transforms per workgroup (csrc/fft_spec.hip, k_spec_stream), the SRC launches in
 parts of 65535 rows (csrc/src_poly.hip, launch_src), the FFT's non-finite
 repair takes 256 transforms per workgroup (csrc/fft_nf.hip, k_nf_small), the
 general cascade flattens B * C lanes over blocks of 256 (csrc/iir.hip), and
@@ -563,7 +563,7 @@ def test_src_second_grid_part_rows_are_the_base_rows(gpu, L, M, K):
 
 # --------------------------------------------------------------------------- F: spectrum / STFT
 # n_fft: (threads of a k_spec_stream workgroup = kSpecTpbx * Plan<log2(n_fft) - 1>::TPT with
-# kSpecTpbx = 2 and TPT = (n_fft / 2) / 16 (csrc/fft.hip), hop)
+# kSpecTpbx = 2 and TPT = (n_fft / 2) / 16 (csrc/fft_spec.hip, csrc/fft_pass.h), hop)
 SPEC_CASES = {64: (4, 1), 256: (16, 4), 2048: (128, 8), 16384: (1024, 64)}
 NF_GROUP = 256           # transforms per k_nf_small workgroup (csrc/fft_nf.hip kNfThreads)
 

@@ -6,7 +6,8 @@ import sys
 import os
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "dsp-audio-project_amd", "csrc")
-files = sys.argv[1:] or ["src_poly.hip", "iir.hip", "fft.hip"]
+files = sys.argv[1:] or ["src_poly.hip", "iir.hip", "fft.hip", "fft_spec.hip", "fft_large.hip",
+                         "fft_dft.hip", "stft_stream.hip"]
 for f in files:
     out = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950",
                           "-I../../include", "-I.", "-c", f, "-o", "/dev/null",
