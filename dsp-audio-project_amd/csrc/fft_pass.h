@@ -1,8 +1,9 @@
 // The in-LDS FFT pass code for gfx950 that every transform family shares:
 // Stockham autosort passes of radix 16 held in registers, one LDS exchange per
 // pass.  Included by fft.hip (k_fft, k_spec_real), fft_spec.hip (k_spec_stream,
-// k_spec_wave12), fft_large.hip (the four-step), fft_dft.hip (Bluestein) and
-// stft_stream.hip (k_stft_stream), and by nothing else.
+// k_spec_wave12), fft_large.hip (the four-step), fft_dft.hip (Bluestein),
+// stft_stream.hip (k_stft_stream) and fft_conv.hip (k_fastconv), and by
+// nothing else.
 //
 // Algorithm (per transform of N = 2^log2n points):
 //   passes p = 0..P-1 with radices R_p (16, except a first pass of 2, 4 or 8
@@ -309,9 +310,17 @@ struct GlobalIO {
   }
 };
 
-template <int LOG2N, int P, class IO, bool LOWREG = false>
+// TWMODE, how a radix-16 pass forms w_r = w1^r: 0 by powering from w1 (w_r =
+// w_(r-1) w1 or w_(r/2)^2); 1 (few live registers) w2, w4, w8 by squaring and
+// w_r as the product of the powers in r's binary digits; 2 the same product
+// with w2, w4, w8 read from the table as well (io.twiddles(), the table the Tw
+// was loaded from at stride 1: 8 m N / (16 Ns) < N/2), so that no twiddle is
+// more than three products away from correctly rounded values -- powering
+// multiplies w1's rounding error by r.
+template <int LOG2N, int P, class IO, int TWMODE = 0>
 __device__ __forceinline__ void run_pass(const IO& io, float2* buf, int j0,
                                          const Tw<LOG2N, P - 1 < 0 ? 0 : P - 1>& tw) {
+  constexpr bool LOWREG = TWMODE != 0;
   using PL = Plan<LOG2N>;
   constexpr int N = PL::N;
   constexpr int R = PL::radix(P);
@@ -320,6 +329,17 @@ __device__ __forceinline__ void run_pass(const IO& io, float2* buf, int j0,
   constexpr int STRIDE = N / R;
   constexpr bool FIRST = P == 0, LAST = P == PL::NP - 1;
   float2 v[NB][R];
+  float2 tp[NB][3];  // TWMODE 2: w2, w4, w8, in flight under the LDS reads
+  if constexpr (TWMODE == 2 && NS > 1) {
+    static_assert(R == 16, "passes after the first are radix 16");
+    const float2* __restrict__ table = io.twiddles();
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      const int i1 = ((j0 + b * PL::TPT) & (NS - 1)) * (N / (NS * R));
+#pragma unroll
+      for (int e = 0; e < 3; ++e) tp[b][e] = table[i1 << (e + 1)];
+    }
+  }
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
     const int j = j0 + b * PL::TPT;
@@ -350,7 +370,10 @@ __device__ __forceinline__ void run_pass(const IO& io, float2* buf, int j0,
       float2 p2[4];
       p2[0] = tw.w[b];
 #pragma unroll
-      for (int e = 1; e < 4; ++e) p2[e] = cmulv(p2[e - 1], p2[e - 1]);
+      for (int e = 1; e < 4; ++e) {
+        if constexpr (TWMODE == 2) p2[e] = tp[b][e - 1];
+        else p2[e] = cmulv(p2[e - 1], p2[e - 1]);
+      }
 #pragma unroll
       for (int r = 1; r < R; ++r) {
         float2 w = make_float2(1.f, 0.f);
@@ -375,8 +398,8 @@ __device__ __forceinline__ void run_pass(const IO& io, float2* buf, int j0,
   }
   if constexpr (!LAST) lds_barrier();
   if constexpr (P + 1 < PL::NP) {
-    if constexpr (P == 0) run_pass<LOG2N, P + 1, IO, LOWREG>(io, buf, j0, tw);
-    else run_pass<LOG2N, P + 1, IO, LOWREG>(io, buf, j0, tw.next);
+    if constexpr (P == 0) run_pass<LOG2N, P + 1, IO, TWMODE>(io, buf, j0, tw);
+    else run_pass<LOG2N, P + 1, IO, TWMODE>(io, buf, j0, tw.next);
   }
 }
 

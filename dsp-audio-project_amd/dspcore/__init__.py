@@ -14,18 +14,22 @@ Layers (bottom-up):
                   (include/dspcore_eqlive.h)
   stspec          stream spectrum: a running spectrogram of a stream, frame by frame
                   (include/dspcore_stspec.h)
+  fastconv        fast convolution: long FIRs by overlap-save on the in-LDS FFT,
+                  one-shot and as a stream (include/dspcore_fastconv.h)
   shard           one host thread per GPU over contiguous channel ranges
   host            numpy batches through the chain with PCIe copies overlapped
 The reference-compatible drop-in is dsp-audio-project_amd/modules/dsp_core.py.
 """
 from . import design  # noqa: F401
 
-__all__ = ["design", "ops", "chain", "stream", "eqbank", "eqlive", "stspec", "shard", "host"]
-__version__ = "1.7.0"
+__all__ = ["design", "ops", "chain", "stream", "eqbank", "eqlive", "stspec", "fastconv", "shard",
+           "host"]
+__version__ = "1.8.0"
 
 
 def __getattr__(name):  # lazy: importing design must not require the GPU library
-    if name in ("ops", "chain", "stream", "eqbank", "eqlive", "stspec", "shard", "host", "_lib"):
+    if name in ("ops", "chain", "stream", "eqbank", "eqlive", "stspec", "fastconv", "shard", "host",
+                "_lib"):
         import importlib
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

@@ -39,8 +39,8 @@ _vp, _dp = ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)
 
 # name -> (restype, argtypes); mirrors include/dspcore.h one to one, then
 # include/dspcore_stream.h, include/dspcore_eqbank.h,
-# include/dspcore_eqlive.h and include/dspcore_stspec.h.  load() requires
-# every one to be exported.
+# include/dspcore_eqlive.h, include/dspcore_stspec.h and
+# include/dspcore_fastconv.h.  load() requires every one to be exported.
 _SIGNATURES = {
     "dsp_version": (ctypes.c_int, []),
     "dsp_last_error": (ctypes.c_char_p, []),
@@ -130,6 +130,12 @@ _SIGNATURES = {
     "dsp_stspec_mag_f32": (ctypes.c_int, [
         _vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _vp, _c_i64, _c_i64, _c_i32, _c_i64, _c_i64,
         _c_i32, _vp, _vp, _vp]),
+    # include/dspcore_fastconv.h
+    "dsp_fastconv_version": (ctypes.c_int, []),
+    "dsp_fastconv_log2n": (ctypes.c_int, [_c_i32]),
+    "dsp_fastconv_f32": (ctypes.c_int, [
+        _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i32,
+        _vp, _c_i32, _vp, _vp]),
 }
 STREAM_HEADER_PATH = os.path.join(REPO_ROOT, "include", "dspcore_stream.h")
 DSP_STREAM_MAX_STAGES = 8
@@ -142,6 +148,8 @@ DSP_EQLIVE_MAX_SLOTS = 8
 DSP_EQLIVE_RECORD_BYTES = 2560
 STSPEC_HEADER_PATH = os.path.join(REPO_ROOT, "include", "dspcore_stspec.h")
 DSP_STSPEC_MIN_LOG2N = 5
+FASTCONV_HEADER_PATH = os.path.join(REPO_ROOT, "include", "dspcore_fastconv.h")
+DSP_FASTCONV_MIN_LOG2N = 6
 DSP_TRACE_NAME = 32
 DSP_WAV_PCM = 1
 DSP_WAV_FLOAT = 3

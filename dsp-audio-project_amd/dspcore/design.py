@@ -638,3 +638,63 @@ def bluestein_tables(n: int) -> tuple[np.ndarray, np.ndarray, int]:
     if n > 1:
         b[M - np.arange(1, n)] = np.conj(chirp[1:])
     return chirp, np.fft.fft(b) / M, M
+
+
+# ---------------------------------------------------------------------------
+# Fast convolution (include/dspcore_fastconv.h)
+# ---------------------------------------------------------------------------
+FASTCONV_MIN_LOG2N = 6
+FASTCONV_MAX_LOG2N = 14
+FASTCONV_MAX_TAPS = (1 << (FASTCONV_MAX_LOG2N - 1)) + 1    # 8193: K <= n_fft / 2 + 1
+# From this many taps on the drop-in takes the FFT path instead of the direct
+# kernel.  Measured on an MI355X (tools/fastconv_probe.py --extra, DESIGN.md
+# section 3.3.2): on 4096 x 48000 samples the direct kernel wins at 9, 17 and
+# 25 taps and loses from 33 on (direct / FFT 0.90 -> 1.26); on one row of
+# 441000 the two are equal within the box's spread up to 33 taps.
+FASTCONV_MIN_TAPS = 33
+
+
+@dataclass(frozen=True)
+class FastConvPlan:
+    """One FIR for dsp_fastconv_f32: K taps on transforms of n_fft = 2^log2n
+    points, hop = n_fft - (K - 1) outputs per block, the float32 taps and hf =
+    FFT(taps zero-padded to n_fft) / n_fft."""
+    K: int
+    log2n: int
+    n_fft: int
+    hop: int
+    taps: np.ndarray       # float32 [K]
+    hf: np.ndarray         # complex64 [n_fft]
+
+
+def fastconv_log2n(K: int) -> int:
+    """dsp_fastconv_log2n's rule: the smallest log2n in 6 .. 14 with 2^log2n >=
+    4 (K - 1); 14 where only that still fits (K <= 8193)."""
+    K = int(K)
+    if K < 1:
+        raise ValueError(f"K={K} < 1")
+    if K > FASTCONV_MAX_TAPS:
+        raise RuntimeError(f"K={K} above {FASTCONV_MAX_TAPS} taps (one 2^14-point transform)")
+    lg = FASTCONV_MIN_LOG2N
+    while lg < FASTCONV_MAX_LOG2N and (1 << lg) < 4 * (K - 1):
+        lg += 1
+    return lg
+
+
+def fastconv_plan(taps, log2n: int | None = None) -> FastConvPlan:
+    """Plans the overlap-save convolution with `taps` (1-D, rounded to float32
+    first: the kernel's direct sums and hf use the same values).  hf is
+    np.fft.fft in float64 of those float32 values, divided by n_fft, rounded
+    once.  Host only."""
+    t32 = np.ascontiguousarray(np.asarray(taps, dtype=np.float64).astype(np.float32))
+    if t32.ndim != 1 or t32.size < 1:
+        raise ValueError(f"taps must be 1-D with at least one tap, got shape {t32.shape}")
+    K = int(t32.size)
+    lg = fastconv_log2n(K) if log2n is None else int(log2n)
+    if not FASTCONV_MIN_LOG2N <= lg <= FASTCONV_MAX_LOG2N:
+        raise RuntimeError(f"log2n={lg} outside [{FASTCONV_MIN_LOG2N}, {FASTCONV_MAX_LOG2N}]")
+    N = 1 << lg
+    if K > N // 2 + 1:
+        raise ValueError(f"K={K} taps need n_fft >= {2 * (K - 1)}, got {N}")
+    hf = (np.fft.fft(t32.astype(np.float64), N) / N).astype(np.complex64)
+    return FastConvPlan(K, lg, N, N - (K - 1), t32, hf)

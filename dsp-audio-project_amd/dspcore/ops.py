@@ -630,3 +630,52 @@ def stft_magnitude(x: torch.Tensor, n_fft: int, hop: int, frames: int,
                                   out.stride(1), _ptr(win), _ptr(tw), _stream(x.device))
     _lib.check(rc, "dsp_stft_mag_f32")
     return out
+
+
+def fastconv_tables(plan, device: torch.device) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(taps, hf, twiddles) of a design.FastConvPlan on `device`, cached."""
+    taps = _cached(("fc_taps", plan.taps.tobytes(), device.index),
+                   lambda: torch.from_numpy(plan.taps).to(device))
+    hf = _cached(("fc_hf", plan.log2n, plan.taps.tobytes(), device.index),
+                 lambda: torch.from_numpy(np.ascontiguousarray(plan.hf).view(np.float32)).to(device))
+    return taps, hf, _table("tw", plan.n_fft, device)
+
+
+def fastconv(x: torch.Tensor, plan, offset: int = 0, n_out: int | None = None,
+             hist_in: torch.Tensor | None = None, hist_out: torch.Tensor | None = None,
+             out: torch.Tensor | None = None, tables=None) -> torch.Tensor:
+    """y[b, m] = sum_t taps[t] s_b[m + offset - t], m < n_out (default n_in), by
+    overlap-save on the in-LDS FFT (dsp_fastconv_f32; plan: a
+    design.FastConvPlan).  s_b is row b of x, zeros after it, and before it
+    hist_in[b, :K - 1] (zeros without one); hist_out[b, :K - 1] receives the
+    last K - 1 samples of (history | row).  float32 CUDA [B, n] rows at any
+    4-byte alignment.  tables: fastconv_tables(plan, device), for a caller that
+    holds them."""
+    x = _rows(x, "x")
+    if x.dtype != torch.float32:
+        x = x.float()
+    B, n_in = x.shape
+    n_out = n_in if n_out is None else int(n_out)
+    if out is None:
+        out = torch.empty((B, n_out), dtype=torch.float32, device=x.device)
+    elif (out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B
+          or out.shape[1] < n_out or out.stride(1) != 1 or out.device != x.device):
+        raise ValueError(f"out must be float32 [{B}, >= {n_out}] on {x.device}")
+    for name, h in (("hist_in", hist_in), ("hist_out", hist_out)):
+        if h is not None and (h.dtype != torch.float32 or h.dim() != 2 or h.shape[0] != B
+                              or h.shape[1] < plan.K - 1 or h.stride(1) != 1
+                              or h.device != x.device):
+            raise ValueError(f"{name} must be float32 [{B}, >= {plan.K - 1}] on {x.device}")
+    if hist_in is not None and hist_out is not None and ld(hist_in) != ld(hist_out):
+        raise ValueError("hist_in and hist_out must have one row pitch")
+    hist = hist_in if hist_in is not None else hist_out
+    taps, hf, tw = fastconv_tables(plan, x.device) if tables is None else tables
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        rc = lib.dsp_fastconv_f32(
+            _ptr(x) if n_in else None, _ptr(out) if n_out else None, B, n_in, ld(x) if n_in else 0,
+            n_out, ld(out) if n_out else 0, int(offset), _ptr(hist_in), _ptr(hist_out),
+            ld(hist) if hist is not None else 0, _ptr(taps), plan.K, _ptr(hf), plan.log2n,
+            _ptr(tw), _stream(x.device))
+    _lib.check(rc, "dsp_fastconv_f32")
+    return out[:, :n_out]

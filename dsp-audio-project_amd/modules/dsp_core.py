@@ -33,8 +33,9 @@ Deliberate differences, documented in DESIGN.md:
   array for N = 3), and RuntimeError above 2^32 points (the reference's
   pure-Python recursion has no limit but takes hours there);
 * keyword-only extensions: conversion_tasa_muestreo(..., num_taps=None) and
-  calcular_espectro_magnitud(..., n_fft=2048); one added function,
-  calcular_espectrograma_magnitud (every frame).
+  calcular_espectro_magnitud(..., n_fft=2048); two added functions,
+  calcular_espectrograma_magnitud (every frame) and
+  convolucion_rapida (np.convolve with a long impulse response).
 """
 from __future__ import annotations
 
@@ -46,7 +47,7 @@ __all__ = [
     "cargar_senal_audio", "fft_diezmado_en_tiempo", "calcular_espectro_magnitud",
     "generar_respuesta_impulso_sinc", "conversion_tasa_muestreo",
     "disenar_coeficientes_diferencias", "aplicar_ecuacion_diferencias",
-    "sistema_ecualizador", "calcular_espectrograma_magnitud",
+    "sistema_ecualizador", "calcular_espectrograma_magnitud", "convolucion_rapida",
 ]
 
 
@@ -324,6 +325,31 @@ def conversion_tasa_muestreo(x_n, fs_original, M, L, *, num_taps=None):
     plan = _design.src_plan(_length(x_n), fs_original, M, L, num_taps)
     ops = _ops()
     return _run(x_n, lambda t, B: ops.src_polyphase(t, plan), np.float64), plan.fs_out
+
+
+def convolucion_rapida(x_n, h, *, modo="same"):
+    """Extension (not in the reference): np.convolve(x_n, h, modo) for a signal
+    (or every row of a [B, n] batch) and a real impulse response h of any
+    length -- a band filter, a room or cabinet response.  modo is np.convolve's
+    'same' or 'full', or 'causal': the first len(x) samples of 'full', which is
+    lfilter(h, 1, x).  From design.FASTCONV_MIN_TAPS taps up to 8193 it runs as
+    overlap-save on the in-LDS FFT (dsp_fastconv_f32), below and above that on
+    the direct kernel (dsp_src_polyphase_f32, L = M = 1); float32 taps either
+    way."""
+    from dspcore.fastconv import mode_geometry
+    taps = np.asarray(h.cpu() if _is_tensor(h) else h, dtype=np.float64)
+    if taps.ndim != 1 or taps.size < 1:
+        raise ValueError(f"h must be 1-D with at least one tap, got shape {taps.shape}")
+    n, K = _length(x_n), int(taps.size)
+    if n < 1:
+        raise ValueError("convolucion_rapida needs at least one sample")
+    offset, n_out = mode_geometry(modo, n, K)
+    ops = _ops()
+    if _design.FASTCONV_MIN_TAPS <= K <= _design.FASTCONV_MAX_TAPS:
+        plan = _design.fastconv_plan(taps)
+        return _run(x_n, lambda t, B: ops.fastconv(t, plan, offset, n_out), np.float64)
+    src = _design.SrcPlan(1, 1, K, taps, offset, n, n_out, 0)
+    return _run(x_n, lambda t, B: ops.src_polyphase(t, src), np.float64)
 
 
 # ---------------------------------------------------------------------------
