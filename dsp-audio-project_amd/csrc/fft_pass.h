@@ -2,8 +2,8 @@
 // Stockham autosort passes of radix 16 held in registers, one LDS exchange per
 // pass.  Included by fft.hip (k_fft, k_spec_real), fft_spec.hip (k_spec_stream,
 // k_spec_wave12), fft_large.hip (the four-step), fft_dft.hip (Bluestein),
-// stft_stream.hip (k_stft_stream) and fft_conv.hip (k_fastconv), and by
-// nothing else.
+// stft_stream.hip (k_stft_stream), fft_conv.hip (k_fastconv) and fft_pconv.hip
+// (k_partconv_fwd, k_partconv_mac), and by nothing else.
 //
 // Algorithm (per transform of N = 2^log2n points):
 //   passes p = 0..P-1 with radices R_p (16, except a first pass of 2, 4 or 8

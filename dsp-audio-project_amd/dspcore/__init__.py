@@ -16,20 +16,22 @@ Layers (bottom-up):
                   (include/dspcore_stspec.h)
   fastconv        fast convolution: long FIRs by overlap-save on the in-LDS FFT,
                   one-shot and as a stream (include/dspcore_fastconv.h)
+  partconv        partitioned fast convolution: FIRs of up to 2^20 taps, one-shot
+                  and as a stream (include/dspcore_partconv.h)
   shard           one host thread per GPU over contiguous channel ranges
   host            numpy batches through the chain with PCIe copies overlapped
 The reference-compatible drop-in is dsp-audio-project_amd/modules/dsp_core.py.
 """
 from . import design  # noqa: F401
 
-__all__ = ["design", "ops", "chain", "stream", "eqbank", "eqlive", "stspec", "fastconv", "shard",
-           "host"]
+__all__ = ["design", "ops", "chain", "stream", "eqbank", "eqlive", "stspec", "fastconv",
+           "partconv", "shard", "host"]
 __version__ = "1.8.0"
 
 
 def __getattr__(name):  # lazy: importing design must not require the GPU library
-    if name in ("ops", "chain", "stream", "eqbank", "eqlive", "stspec", "fastconv", "shard", "host",
-                "_lib"):
+    if name in ("ops", "chain", "stream", "eqbank", "eqlive", "stspec", "fastconv", "partconv",
+                "shard", "host", "_lib"):
         import importlib
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

@@ -39,8 +39,9 @@ _vp, _dp = ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)
 
 # name -> (restype, argtypes); mirrors include/dspcore.h one to one, then
 # include/dspcore_stream.h, include/dspcore_eqbank.h,
-# include/dspcore_eqlive.h, include/dspcore_stspec.h and
-# include/dspcore_fastconv.h.  load() requires every one to be exported.
+# include/dspcore_eqlive.h, include/dspcore_stspec.h,
+# include/dspcore_fastconv.h and include/dspcore_partconv.h.  load() requires
+# every one to be exported.
 _SIGNATURES = {
     "dsp_version": (ctypes.c_int, []),
     "dsp_last_error": (ctypes.c_char_p, []),
@@ -136,6 +137,17 @@ _SIGNATURES = {
     "dsp_fastconv_f32": (ctypes.c_int, [
         _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _c_i32,
         _vp, _c_i32, _vp, _vp]),
+    # include/dspcore_partconv.h
+    "dsp_partconv_version": (ctypes.c_int, []),
+    "dsp_partconv_log2n": (ctypes.c_int, [_c_i32]),
+    "dsp_partconv_hist_len": (_c_i64, [_c_i32, _c_i32]),
+    "dsp_partconv_slots": (_c_i64, [_c_i32, _c_i32, _c_i64, _c_i64]),
+    "dsp_partconv_workspace_bytes": (_c_sz, [_c_i64, _c_i32, _c_i64]),
+    "dsp_partconv_f32": (ctypes.c_int, [
+        _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp,
+        _c_i32, _vp, _c_i32, _vp, _c_sz, _c_i64, _vp, _vp]),
+    "dsp_partconv_prime_f32": (ctypes.c_int, [
+        _vp, _c_i64, _c_i64, _c_i64, _c_i32, _c_i32, _vp, _c_sz, _c_i64, _vp, _vp]),
 }
 STREAM_HEADER_PATH = os.path.join(REPO_ROOT, "include", "dspcore_stream.h")
 DSP_STREAM_MAX_STAGES = 8
@@ -150,6 +162,9 @@ STSPEC_HEADER_PATH = os.path.join(REPO_ROOT, "include", "dspcore_stspec.h")
 DSP_STSPEC_MIN_LOG2N = 5
 FASTCONV_HEADER_PATH = os.path.join(REPO_ROOT, "include", "dspcore_fastconv.h")
 DSP_FASTCONV_MIN_LOG2N = 6
+PARTCONV_HEADER_PATH = os.path.join(REPO_ROOT, "include", "dspcore_partconv.h")
+DSP_PARTCONV_MAX_TAPS = 1 << 20
+DSP_PARTCONV_MAX_PARTS = 1024
 DSP_TRACE_NAME = 32
 DSP_WAV_PCM = 1
 DSP_WAV_FLOAT = 3

@@ -698,3 +698,72 @@ def fastconv_plan(taps, log2n: int | None = None) -> FastConvPlan:
         raise ValueError(f"K={K} taps need n_fft >= {2 * (K - 1)}, got {N}")
     hf = (np.fft.fft(t32.astype(np.float64), N) / N).astype(np.complex64)
     return FastConvPlan(K, lg, N, N - (K - 1), t32, hf)
+
+
+# ---------------------------------------------------------------------------
+# Partitioned fast convolution (include/dspcore_partconv.h)
+# ---------------------------------------------------------------------------
+PARTCONV_MAX_TAPS = 1 << 20
+PARTCONV_MAX_PARTS = 1024
+
+
+@dataclass(frozen=True)
+class PartConvPlan:
+    """One FIR for dsp_partconv_f32: K taps as S partitions of P = n_fft / 2 on
+    transforms of n_fft = 2^log2n points; `hop` = P outputs come from each pair
+    of blocks; hist_len = S * P + 3 * n_fft / 4 samples of history per row;
+    the float32 taps and hf[s] = FFT(taps[s P : s P + P] zero-padded to n_fft)
+    / n_fft."""
+    K: int
+    log2n: int
+    n_fft: int
+    P: int
+    S: int
+    hist_len: int
+    taps: np.ndarray       # float32 [K]
+    hf: np.ndarray         # complex64 [S, n_fft]
+
+    @property
+    def N(self) -> int:
+        return self.n_fft
+
+    @property
+    def hop(self) -> int:
+        return self.P
+
+
+def partconv_log2n(K: int) -> int:
+    """dsp_partconv_log2n's rule: the smallest log2n in 6 .. 14 with 2^log2n / 2
+    >= K (one partition), and 14 above 8192 taps: the fastest size measured at
+    16384, 65536 and 262144 taps (tools/partconv_probe.py, DESIGN.md section
+    3.3.3)."""
+    K = int(K)
+    if not 1 <= K <= PARTCONV_MAX_TAPS:
+        raise ValueError(f"K={K} outside [1, {PARTCONV_MAX_TAPS}]")
+    lg = FASTCONV_MIN_LOG2N
+    while lg < FASTCONV_MAX_LOG2N and (1 << (lg - 1)) < K:
+        lg += 1
+    return lg
+
+
+def partconv_plan(taps, log2n: int | None = None) -> PartConvPlan:
+    """Plans the partitioned overlap-save convolution with `taps` (1-D, rounded
+    to float32 first: the kernel's direct sums and hf use the same values).
+    hf[s] is np.fft.fft in float64 of partition s of those float32 values,
+    divided by n_fft, rounded once.  Host only."""
+    t32 = np.ascontiguousarray(np.asarray(taps, dtype=np.float64).astype(np.float32))
+    if t32.ndim != 1 or t32.size < 1:
+        raise ValueError(f"taps must be 1-D with at least one tap, got shape {t32.shape}")
+    K = int(t32.size)
+    lg = partconv_log2n(K) if log2n is None else int(log2n)
+    if not FASTCONV_MIN_LOG2N <= lg <= FASTCONV_MAX_LOG2N:
+        raise RuntimeError(f"log2n={lg} outside [{FASTCONV_MIN_LOG2N}, {FASTCONV_MAX_LOG2N}]")
+    N = 1 << lg
+    P = N // 2
+    S = -(-K // P)
+    if S > PARTCONV_MAX_PARTS:
+        raise ValueError(f"K={K} taps are {S} partitions of {P}, above {PARTCONV_MAX_PARTS}")
+    parts = np.zeros((S, P), dtype=np.float64)
+    parts.reshape(-1)[:K] = t32
+    hf = (np.fft.fft(parts, N, axis=-1) / N).astype(np.complex64)
+    return PartConvPlan(K, lg, N, P, S, S * P + 3 * (N // 4), t32, hf)

@@ -679,3 +679,95 @@ def fastconv(x: torch.Tensor, plan, offset: int = 0, n_out: int | None = None,
             _ptr(tw), _stream(x.device))
     _lib.check(rc, "dsp_fastconv_f32")
     return out[:, :n_out]
+
+
+def partconv_tables(plan, device: torch.device) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(taps, hf, twiddles) of a design.PartConvPlan on `device`, cached."""
+    taps = _cached(("fc_taps", plan.taps.tobytes(), device.index),
+                   lambda: torch.from_numpy(plan.taps).to(device))
+    hf = _cached(("pc_hf", plan.log2n, plan.taps.tobytes(), device.index),
+                 lambda: torch.from_numpy(np.ascontiguousarray(plan.hf).view(np.float32)).to(device))
+    return taps, hf, _table("tw", plan.n_fft, device)
+
+
+def partconv_slots(plan, n: int, offset: int = 0) -> int:
+    """Ring slots that suffice for every call with at most n samples in and
+    out at this offset (dsp_partconv_slots)."""
+    rc = _lib.load().dsp_partconv_slots(plan.K, plan.log2n, int(n), int(offset))
+    if rc < 0:
+        _lib.check(int(rc), "dsp_partconv_slots")
+    return int(rc)
+
+
+def partconv_workspace(plan, B: int, slots: int, device: torch.device) -> torch.Tensor:
+    """An uninitialised ring for B rows (uint8; spectra, then flags)."""
+    nbytes = _lib.load().dsp_partconv_workspace_bytes(int(B), plan.log2n, int(slots))
+    return torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=device)
+
+
+def _partconv_hist(h, name, B, plan, device):
+    if h is not None and (h.dtype != torch.float32 or h.dim() != 2 or h.shape[0] != B
+                          or h.shape[1] < plan.hist_len or h.stride(1) != 1
+                          or h.device != device):
+        raise ValueError(f"{name} must be float32 [{B}, >= {plan.hist_len}] on {device}")
+
+
+def partconv(x: torch.Tensor, plan, offset: int = 0, n_out: int | None = None, pos: int = 0,
+             hist_in: torch.Tensor | None = None, hist_out: torch.Tensor | None = None,
+             ws: torch.Tensor | None = None, slots: int | None = None,
+             out: torch.Tensor | None = None, tables=None) -> torch.Tensor:
+    """y[b, m] = sum_t taps[t] s_b[m + offset - t], m < n_out (default n_in), by
+    partitioned overlap-save on the in-LDS FFT (dsp_partconv_f32; plan: a
+    design.PartConvPlan).  s_b is row b of x, zeros after it, and before it
+    hist_in[b, :hist_len] when pos > 0 (zeros at pos = 0, the start of a
+    stream); hist_out[b, :hist_len] receives the last hist_len samples of
+    (history | row).  ws / slots: the spectra ring (partconv_workspace,
+    partconv_slots), which a stream keeps between calls; without one the call
+    allocates its own.  float32 CUDA [B, n] rows at any 4-byte alignment.
+    tables: partconv_tables(plan, device), for a caller that holds them."""
+    x = _rows(x, "x")
+    if x.dtype != torch.float32:
+        x = x.float()
+    B, n_in = x.shape
+    n_out = n_in if n_out is None else int(n_out)
+    if out is None:
+        out = torch.empty((B, n_out), dtype=torch.float32, device=x.device)
+    elif (out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B
+          or out.shape[1] < n_out or out.stride(1) != 1 or out.device != x.device):
+        raise ValueError(f"out must be float32 [{B}, >= {n_out}] on {x.device}")
+    _partconv_hist(hist_in, "hist_in", B, plan, x.device)
+    _partconv_hist(hist_out, "hist_out", B, plan, x.device)
+    if hist_in is not None and hist_out is not None and ld(hist_in) != ld(hist_out):
+        raise ValueError("hist_in and hist_out must have one row pitch")
+    hist = hist_in if hist_in is not None else hist_out
+    if ws is None:
+        if pos:
+            raise ValueError("a call at pos > 0 continues a stream and needs its ring (ws, slots)")
+        slots = partconv_slots(plan, max(n_in, n_out), offset)
+        ws = partconv_workspace(plan, B, slots, x.device)
+    elif slots is None or ws.device != x.device or not ws.is_contiguous():
+        raise ValueError(f"ws must be a contiguous buffer on {x.device}, with its slot count")
+    taps, hf, tw = partconv_tables(plan, x.device) if tables is None else tables
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        rc = lib.dsp_partconv_f32(
+            _ptr(x) if n_in else None, _ptr(out) if n_out else None, B, n_in, ld(x) if n_in else 0,
+            n_out, ld(out) if n_out else 0, int(offset), int(pos), _ptr(hist_in), _ptr(hist_out),
+            ld(hist) if hist is not None else 0, _ptr(taps), plan.K, _ptr(hf), plan.log2n,
+            _ptr(ws), ws.numel() * ws.element_size(), int(slots), _ptr(tw), _stream(x.device))
+    _lib.check(rc, "dsp_partconv_f32")
+    return out[:, :n_out]
+
+
+def partconv_prime(hist: torch.Tensor, plan, pos: int, ws: torch.Tensor, slots: int) -> None:
+    """Rebuilds a stream's ring at `pos` samples from hist [B, >= hist_len], the
+    samples before pos (dsp_partconv_prime_f32)."""
+    B = int(hist.shape[0])
+    _partconv_hist(hist, "hist", B, plan, hist.device)
+    tw = _table("tw", plan.n_fft, hist.device)
+    lib = _lib.load()
+    with torch.cuda.device(hist.device):
+        rc = lib.dsp_partconv_prime_f32(_ptr(hist), B, ld(hist), int(pos), plan.K, plan.log2n,
+                                        _ptr(ws), ws.numel() * ws.element_size(), int(slots),
+                                        _ptr(tw), _stream(hist.device))
+    _lib.check(rc, "dsp_partconv_prime_f32")

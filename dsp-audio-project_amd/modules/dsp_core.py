@@ -333,9 +333,9 @@ def convolucion_rapida(x_n, h, *, modo="same"):
     length -- a band filter, a room or cabinet response.  modo is np.convolve's
     'same' or 'full', or 'causal': the first len(x) samples of 'full', which is
     lfilter(h, 1, x).  From design.FASTCONV_MIN_TAPS taps up to 8193 it runs as
-    overlap-save on the in-LDS FFT (dsp_fastconv_f32), below and above that on
-    the direct kernel (dsp_src_polyphase_f32, L = M = 1); float32 taps either
-    way."""
+    overlap-save on the in-LDS FFT (dsp_fastconv_f32), from 8194 up to 2^20 taps
+    as partitioned overlap-save (dsp_partconv_f32), below and above that on the
+    direct kernel (dsp_src_polyphase_f32, L = M = 1); float32 taps every way."""
     from dspcore.fastconv import mode_geometry
     taps = np.asarray(h.cpu() if _is_tensor(h) else h, dtype=np.float64)
     if taps.ndim != 1 or taps.size < 1:
@@ -348,6 +348,9 @@ def convolucion_rapida(x_n, h, *, modo="same"):
     if _design.FASTCONV_MIN_TAPS <= K <= _design.FASTCONV_MAX_TAPS:
         plan = _design.fastconv_plan(taps)
         return _run(x_n, lambda t, B: ops.fastconv(t, plan, offset, n_out), np.float64)
+    if _design.FASTCONV_MAX_TAPS < K <= _design.PARTCONV_MAX_TAPS:
+        pplan = _design.partconv_plan(taps)
+        return _run(x_n, lambda t, B: ops.partconv(t, pplan, offset, n_out), np.float64)
     src = _design.SrcPlan(1, 1, K, taps, offset, n, n_out, 0)
     return _run(x_n, lambda t, B: ops.src_polyphase(t, src), np.float64)
 
