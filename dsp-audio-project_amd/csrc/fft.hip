@@ -95,24 +95,10 @@ int launch_one(const FftArgs& a, hipStream_t s) {
 
 template <int MODE>
 int dispatch(const FftArgs& a, int log2n, hipStream_t s) {
-  switch (log2n) {
-    case 0: return launch_one<MODE, 0>(a, s);
-    case 1: return launch_one<MODE, 1>(a, s);
-    case 2: return launch_one<MODE, 2>(a, s);
-    case 3: return launch_one<MODE, 3>(a, s);
-    case 4: return launch_one<MODE, 4>(a, s);
-    case 5: return launch_one<MODE, 5>(a, s);
-    case 6: return launch_one<MODE, 6>(a, s);
-    case 7: return launch_one<MODE, 7>(a, s);
-    case 8: return launch_one<MODE, 8>(a, s);
-    case 9: return launch_one<MODE, 9>(a, s);
-    case 10: return launch_one<MODE, 10>(a, s);
-    case 11: return launch_one<MODE, 11>(a, s);
-    case 12: return launch_one<MODE, 12>(a, s);
-    case 13: return launch_one<MODE, 13>(a, s);
-    case 14: return launch_one<MODE, 14>(a, s);
-    default: return set_error(DSP_EINVAL, "log2n=%d outside [0, %d]", log2n, DSP_MAX_LOG2N);
-  }
+  if (log2n < 0 || log2n > DSP_MAX_LOG2N)
+    return set_error(DSP_EINVAL, "log2n=%d outside [0, %d]", log2n, DSP_MAX_LOG2N);
+  return dispatch_log2n<0, DSP_MAX_LOG2N>(
+      log2n, [&](auto lg) { return launch_one<MODE, decltype(lg)::value>(a, s); });
 }
 
 // The spectrum and the STFT: below 32 points the complex transform, then the

@@ -35,7 +35,7 @@
 // History workgroups (the blockIdx.x after the transforms') copy the last
 // K - 1 samples of (history | row) into hist_out, a buffer nothing in the
 // launch reads.
-#include "fft_pass.h"
+#include "fft_conv_common.h"
 #include "dspcore_fastconv.h"
 
 namespace dsp {
@@ -54,19 +54,11 @@ struct FcArgs {
   int K, V;
 };
 
-// Sample i >= -(K - 1) of row `row`'s stream.
-struct FcRow {
-  const float* x;  // the row's sample 0
-  const float* h;  // h[i], i < 0: the history (nullptr: zeros)
-  int64_t n_in;
-  __device__ __forceinline__ float at(int64_t i) const {
-    return i < 0 ? (h ? h[i] : 0.f) : (i < n_in ? x[i] : 0.f);
-  }
-};
+// Sample i >= -(K - 1) of row `row`'s stream: nothing reads further back.
+using FcRow = ConvRow<false>;
 
 __device__ __forceinline__ FcRow fc_row(const FcArgs& a, int64_t row) {
-  return FcRow{a.x + row * a.ld_x,
-               a.hist_in ? a.hist_in + row * a.ld_hist + (a.K - 1) : nullptr, a.n_in};
+  return conv_row<false>(a, a.K - 1, row);
 }
 
 // The N samples of one block: n < nc from the history, n < nv from x, then 0.
@@ -87,10 +79,6 @@ __device__ __forceinline__ FcWin fc_win(const FcRow& r, int64_t s0) {
   return FcWin{r.h ? r.h + s0 : nullptr, r.x + s0, nc, nv};
 }
 
-__device__ __forceinline__ bool fc_nonfinite(float v) {
-  return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;
-}
-
 // Stage 1: z from memory, C = conj(A * Hf) into LDS.
 template <int N>
 struct FcStage1 {
@@ -106,7 +94,7 @@ struct FcStage1 {
     if (!live) return make_float2(0.f, 0.f);
     const float re = w1.at(n);
     const float im = second ? w2.at(n) : 0.f;
-    if (fc_nonfinite(re) || fc_nonfinite(im)) *flag = 1;
+    if (conv_nonfinite(re) || conv_nonfinite(im)) *flag = 1;
     return make_float2(re, im);
   }
   __device__ __forceinline__ void store(int k, float2 v) const {
@@ -141,14 +129,7 @@ __global__ __launch_bounds__(Plan<LOG2N>::NT) void k_fastconv(FcArgs a, unsigned
   extern __shared__ __attribute__((aligned(16))) float2 lds[];
   __shared__ int s_flag[PL::TPB];
   if (blockIdx.x >= tgroups) {
-    // history update: element e = (row, j) of hist_out
-    const int64_t k1 = a.K - 1;
-    const int64_t total = a.B * k1;
-    const int64_t step = (int64_t)(gridDim.x - tgroups) * PL::NT;
-    for (int64_t e = (int64_t)(blockIdx.x - tgroups) * PL::NT + threadIdx.x; e < total; e += step) {
-      const int64_t row = e / k1, j = e - row * k1;
-      a.hist_out[row * a.ld_hist + j] = fc_row(a, row).at(a.n_in - k1 + j);
-    }
+    conv_copy_history<PL::NT, false>(a, a.K - 1, tgroups);
     return;
   }
   const int tl = threadIdx.x / PL::TPT;
@@ -180,16 +161,10 @@ __global__ __launch_bounds__(Plan<LOG2N>::NT) void k_fastconv(FcArgs a, unsigned
       FcStage2<PL::N>{buf, a.tw, y, a.K - 1, a.V, fft_out ? n1 : 0, fft_out ? n2 : 0}, buf, j0, tw);
   if (!live || !bad) return;
   // the flagged transform's outputs, directly (no barrier from here on)
-  for (int m = j0; m < n1 + n2; m += PL::TPT) {
-    const int64_t i0 = m0 + m + a.offset;
-    double acc = 0.0;
-#pragma unroll 1
-    for (int tp = 0; tp < a.K; ++tp) acc = fma((double)a.taps[tp], (double)r.at(i0 - tp), acc);
-    y[m] = (float)acc;
-  }
+  for (int m = j0; m < n1 + n2; m += PL::TPT)
+    conv_direct(y + m, r, a.taps, a.K, m0 + m + a.offset);
 }
 
-constexpr int64_t kFcHistGroups = 1024;  // at most; the copy is grid-strided
 constexpr int kFcMinLog2 = 6;
 constexpr int kFcMaxTaps = (1 << (DSP_MAX_LOG2N - 1)) + 1;
 
@@ -198,11 +173,7 @@ int launch_fastconv_n(const FcArgs& a, hipStream_t s) {
   using PL = Plan<LOG2N>;
   const int64_t transforms = a.B * a.pairs;
   const int64_t tg = ceil_div(transforms, PL::TPB);
-  int64_t cg = 0;
-  if (a.hist_out && a.K > 1) {
-    cg = ceil_div(a.B * (a.K - 1), 4 * PL::NT);
-    cg = cg < 1 ? 1 : (cg > kFcHistGroups ? kFcHistGroups : cg);
-  }
+  const int64_t cg = conv_hist_groups(a.hist_out, a.B, a.K - 1, PL::NT);
   DSP_REQUIRE(tg + cg <= INT32_MAX, "too many blocks in one call");
   if (tg + cg == 0) return DSP_OK;
   return launch_lds_resident<PL>(k_fastconv<LOG2N>, "k_fastconv", transforms, cg, s, a,
@@ -210,18 +181,8 @@ int launch_fastconv_n(const FcArgs& a, hipStream_t s) {
 }
 
 int launch_fastconv(const FcArgs& a, int log2n, hipStream_t s) {
-  switch (log2n) {
-    case 6: return launch_fastconv_n<6>(a, s);
-    case 7: return launch_fastconv_n<7>(a, s);
-    case 8: return launch_fastconv_n<8>(a, s);
-    case 9: return launch_fastconv_n<9>(a, s);
-    case 10: return launch_fastconv_n<10>(a, s);
-    case 11: return launch_fastconv_n<11>(a, s);
-    case 12: return launch_fastconv_n<12>(a, s);
-    case 13: return launch_fastconv_n<13>(a, s);
-    case 14: return launch_fastconv_n<14>(a, s);
-    default: return set_error(DSP_ENOTSUP, "log2n=%d outside [6, 14]", log2n);
-  }
+  return dispatch_log2n<kFcMinLog2, DSP_MAX_LOG2N>(
+      log2n, [&](auto lg) { return launch_fastconv_n<decltype(lg)::value>(a, s); });
 }
 
 int fastconv_log2n(int K) {
@@ -234,12 +195,6 @@ int fastconv_log2n(int K) {
   return lg;
 }
 
-// Whether [p, p + n) and [q, q + m) floats share a byte.
-bool fc_overlap(const float* p, int64_t n, const float* q, int64_t m) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return n > 0 && m > 0 && a < b + 4 * (uintptr_t)m && b < a + 4 * (uintptr_t)n;
-}
-
 int fastconv(const float* x, float* y, int64_t B, int64_t n_in, int64_t ld_x, int64_t n_out,
              int64_t ld_y, int64_t offset, const float* hist_in, float* hist_out, int64_t ld_hist,
              const float* taps, int K, const float* hf, int log2n, const float* twiddles,
@@ -249,26 +204,11 @@ int fastconv(const float* x, float* y, int64_t B, int64_t n_in, int64_t ld_x, in
   const int64_t N = int64_t(1) << log2n;
   DSP_REQUIRE(K >= 1 && K <= N / 2 + 1, "K=%d outside [1, n_fft / 2 + 1 = %lld]", K,
               (long long)(N / 2 + 1));
-  DSP_REQUIRE(B >= 0 && n_in >= 0 && n_out >= 0, "negative count B=%lld n_in=%lld n_out=%lld",
-              (long long)B, (long long)n_in, (long long)n_out);
-  DSP_REQUIRE(offset >= 0 && offset <= K - 1, "offset=%lld outside [0, K - 1 = %d]",
-              (long long)offset, K - 1);
-  DSP_REQUIRE(n_in <= (int64_t(1) << 40), "n_in=%lld > 2^40", (long long)n_in);
-  DSP_REQUIRE(n_out <= n_in + (K - 1) - offset, "n_out=%lld > n_in + K - 1 - offset = %lld",
-              (long long)n_out, (long long)(n_in + (K - 1) - offset));
-  DSP_REQUIRE(ld_x >= n_in && ld_y >= n_out, "leading dimension too small (ld_x=%lld ld_y=%lld)",
-              (long long)ld_x, (long long)ld_y);
-  DSP_REQUIRE((!hist_in && !hist_out) || ld_hist >= K - 1, "ld_hist=%lld < K - 1 = %d",
-              (long long)ld_hist, K - 1);
-  DSP_REQUIRE(hist_in != hist_out || !hist_in, "hist_in and hist_out are one buffer");
+  if (int rc = conv_check_io(x, y, B, n_in, ld_x, n_out, ld_y, offset, hist_in, hist_out, ld_hist,
+                             K - 1, K))
+    return rc;
   if (B == 0) return DSP_OK;
   DSP_REQUIRE(taps && hf && twiddles, "null pointer");
-  DSP_REQUIRE(x || n_in == 0, "null x");
-  DSP_REQUIRE(y || n_out == 0, "null y");
-  DSP_REQUIRE(B <= (int64_t(1) << 40) / (ld_x > ld_y ? (ld_x > 1 ? ld_x : 1) : (ld_y > 1 ? ld_y : 1)),
-              "batch too large");
-  DSP_REQUIRE(!fc_overlap(x, (B - 1) * ld_x + n_in, y, (B - 1) * ld_y + n_out),
-              "x and y overlap");
   DSP_REQUIRE((reinterpret_cast<uintptr_t>(hf) & 7) == 0 &&
                   (reinterpret_cast<uintptr_t>(twiddles) & 7) == 0,
               "hf and twiddles must be 8-byte aligned");

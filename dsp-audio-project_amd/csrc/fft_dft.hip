@@ -98,23 +98,11 @@ int launch_dft(const float* in, float* out, int64_t B, int64_t n, int real_in, i
   BluArgs a{in, out, B, n, ld_in, ld_out, real_in, reinterpret_cast<const float2*>(chirp),
             reinterpret_cast<const float2*>(chirp_fft), reinterpret_cast<const float2*>(tw_m)};
   TraceScope trace("dft", s);
-  switch (bluestein_log2m(n)) {
-    case 1: return launch_blu<1>(a, s);
-    case 2: return launch_blu<2>(a, s);
-    case 3: return launch_blu<3>(a, s);
-    case 4: return launch_blu<4>(a, s);
-    case 5: return launch_blu<5>(a, s);
-    case 6: return launch_blu<6>(a, s);
-    case 7: return launch_blu<7>(a, s);
-    case 8: return launch_blu<8>(a, s);
-    case 9: return launch_blu<9>(a, s);
-    case 10: return launch_blu<10>(a, s);
-    case 11: return launch_blu<11>(a, s);
-    case 12: return launch_blu<12>(a, s);
-    case 13: return launch_blu<13>(a, s);
-    case 14: return launch_blu<14>(a, s);
-    default: return set_error(DSP_EINVAL, "no Bluestein size for n=%lld", (long long)n);
-  }
+  const int lg2m = bluestein_log2m(n);
+  if (lg2m > DSP_MAX_LOG2N)
+    return set_error(DSP_EINVAL, "no Bluestein size for n=%lld", (long long)n);
+  return dispatch_log2n<1, DSP_MAX_LOG2N>(
+      lg2m, [&](auto lg) { return launch_blu<decltype(lg)::value>(a, s); });
 }
 
 }  // namespace dsp

@@ -2,8 +2,9 @@
 // Stockham autosort passes of radix 16 held in registers, one LDS exchange per
 // pass.  Included by fft.hip (k_fft, k_spec_real), fft_spec.hip (k_spec_stream,
 // k_spec_wave12), fft_large.hip (the four-step), fft_dft.hip (Bluestein),
-// stft_stream.hip (k_stft_stream), fft_conv.hip (k_fastconv) and fft_pconv.hip
-// (k_partconv_fwd, k_partconv_mac), and by nothing else.
+// stft_stream.hip (k_stft_stream) and, through fft_conv_common.h, fft_conv.hip
+// (k_fastconv) and fft_pconv.hip (k_partconv_fwd, k_partconv_mac), and by
+// nothing else.
 //
 // Algorithm (per transform of N = 2^log2n points):
 //   passes p = 0..P-1 with radices R_p (16, except a first pass of 2, 4 or 8
@@ -28,6 +29,8 @@
 // The spectrum mode also runs a framed STFT: transform t = (row, frame) reads
 // the window-weighted frame starting hop*frame samples into the row's segment.
 #pragma once
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -448,6 +451,18 @@ int launch_lds_resident(Kern kernel, const char* name, int64_t transforms, int64
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(PL::NT), shm, s, args...);
   DSP_LAUNCHED(name);
   return DSP_OK;
+}
+
+// Host: f(std::integral_constant<int, L>{}) for L = log2n in [LO, HI], the
+// launchers' switch over their kernels' template argument; DSP_ENOTSUP outside.
+template <int LO, int HI, int L = LO, class F>
+int dispatch_log2n(int log2n, F&& f) {
+  if constexpr (L > HI) {
+    return set_error(DSP_ENOTSUP, "log2n=%d outside [%d, %d]", log2n, LO, HI);
+  } else {
+    if (log2n == L) return f(std::integral_constant<int, L>{});
+    return dispatch_log2n<LO, HI, L + 1>(log2n, f);
+  }
 }
 
 }  // namespace

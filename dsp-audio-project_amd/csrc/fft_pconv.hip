@@ -35,7 +35,7 @@
 // k_fastconv's fallback does.  They read the K - 1 samples before the output
 // from (history | row), which is why the stream carries the time-domain
 // history as well as the spectra.
-#include "fft_pass.h"
+#include "fft_conv_common.h"
 #include "dspcore_partconv.h"
 
 namespace dsp {
@@ -58,23 +58,12 @@ struct PcArgs {
   int K, S;
 };
 
-// Sample i (relative to the call's x[0]) of row `row`'s stream.
-struct PcRow {
-  const float* x;  // the row's sample 0
-  const float* h;  // h[i], -L <= i < 0: the history (nullptr: zeros)
-  int64_t n_in, L;
-  __device__ __forceinline__ float at(int64_t i) const {
-    return i < 0 ? (h && i >= -L ? h[i] : 0.f) : (i < n_in ? x[i] : 0.f);
-  }
-};
+// Sample i (relative to the call's x[0]) of row `row`'s stream: zeros before
+// the L samples of history (the first pairs of a stream reach behind them).
+using PcRow = ConvRow<true>;
 
 __device__ __forceinline__ PcRow pc_row(const PcArgs& a, int64_t row) {
-  return PcRow{a.x + row * a.ld_x, a.hist_in ? a.hist_in + row * a.ld_hist + a.L : nullptr,
-               a.n_in, a.L};
-}
-
-__device__ __forceinline__ bool pc_nonfinite(float v) {
-  return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;
+  return conv_row<true>(a, a.L, row);
 }
 
 // Forward: z from memory, Z_q to the ring.
@@ -92,7 +81,7 @@ struct PcFwd {
     if (!live) return make_float2(0.f, 0.f);
     const float re = r.at(i0 + n);
     const float im = r.at(i0 + N / 4 + n);
-    if (pc_nonfinite(re) || pc_nonfinite(im)) *flag = 1;
+    if (conv_nonfinite(re) || conv_nonfinite(im)) *flag = 1;
     return make_float2(re, im);
   }
   __device__ __forceinline__ void store(int k, float2 v) const {
@@ -108,13 +97,7 @@ __global__ __launch_bounds__(Plan<LOG2N>::NT) void k_partconv_fwd(PcArgs a, unsi
   extern __shared__ __attribute__((aligned(16))) float2 lds[];
   __shared__ int s_flag[PL::TPB];
   if (blockIdx.x >= tgroups) {
-    // history update: element e = (row, j) of hist_out
-    const int64_t total = a.B * a.L;
-    const int64_t step = (int64_t)(gridDim.x - tgroups) * PL::NT;
-    for (int64_t e = (int64_t)(blockIdx.x - tgroups) * PL::NT + threadIdx.x; e < total; e += step) {
-      const int64_t row = e / a.L, j = e - row * a.L;
-      a.hist_out[row * a.ld_hist + j] = pc_row(a, row).at(a.n_in - a.L + j);
-    }
+    conv_copy_history<PL::NT, true>(a, a.L, tgroups);
     return;
   }
   const int tl = threadIdx.x / PL::TPT;
@@ -221,16 +204,10 @@ __global__ __launch_bounds__(Plan<LOG2N>::NT) void k_partconv_mac(PcArgs a) {
   const PcRow r = pc_row(a, row);
   for (int m = j0; m < N / 2; m += PL::TPT) {
     const int64_t mo = m0 + m;
-    if (mo < 0 || mo >= a.n_out) continue;
-    const int64_t i0 = mo + a.offset;
-    double acc = 0.0;
-#pragma unroll 1
-    for (int tp = 0; tp < a.K; ++tp) acc = fma((double)a.taps[tp], (double)r.at(i0 - tp), acc);
-    y[mo] = (float)acc;
+    if (mo >= 0 && mo < a.n_out) conv_direct(y + mo, r, a.taps, a.K, mo + a.offset);
   }
 }
 
-constexpr int64_t kPcHistGroups = 1024;  // at most; the copy is grid-strided
 constexpr int kPcMinLog2 = 6;
 
 template <int LOG2N>
@@ -238,11 +215,7 @@ int launch_fwd_n(const PcArgs& a, hipStream_t s) {
   using PL = Plan<LOG2N>;
   const int64_t transforms = a.B * a.pairs;
   const int64_t tg = ceil_div(transforms, PL::TPB);
-  int64_t cg = 0;
-  if (a.hist_out && a.L > 0) {
-    cg = ceil_div(a.B * a.L, 4 * PL::NT);
-    cg = cg < 1 ? 1 : (cg > kPcHistGroups ? kPcHistGroups : cg);
-  }
+  const int64_t cg = conv_hist_groups(a.hist_out, a.B, a.L, PL::NT);
   DSP_REQUIRE(tg + cg <= INT32_MAX, "too many blocks in one call");
   if (tg + cg == 0) return DSP_OK;
   TraceScope trace("partconv_fwd", s);
@@ -260,22 +233,14 @@ int launch_mac_n(const PcArgs& a, hipStream_t s) {
   return launch_lds_resident<PL>(k_partconv_mac<LOG2N>, "k_partconv_mac", transforms, 0, s, a);
 }
 
-#define PC_SWITCH(fn, a, s)                                                          \
-  switch (log2n) {                                                                   \
-    case 6: return fn<6>(a, s);                                                      \
-    case 7: return fn<7>(a, s);                                                      \
-    case 8: return fn<8>(a, s);                                                      \
-    case 9: return fn<9>(a, s);                                                      \
-    case 10: return fn<10>(a, s);                                                    \
-    case 11: return fn<11>(a, s);                                                    \
-    case 12: return fn<12>(a, s);                                                    \
-    case 13: return fn<13>(a, s);                                                    \
-    case 14: return fn<14>(a, s);                                                    \
-    default: return set_error(DSP_ENOTSUP, "log2n=%d outside [6, 14]", log2n);       \
-  }
-
-int launch_fwd(const PcArgs& a, int log2n, hipStream_t s) { PC_SWITCH(launch_fwd_n, a, s) }
-int launch_mac(const PcArgs& a, int log2n, hipStream_t s) { PC_SWITCH(launch_mac_n, a, s) }
+int launch_fwd(const PcArgs& a, int log2n, hipStream_t s) {
+  return dispatch_log2n<kPcMinLog2, DSP_MAX_LOG2N>(
+      log2n, [&](auto lg) { return launch_fwd_n<decltype(lg)::value>(a, s); });
+}
+int launch_mac(const PcArgs& a, int log2n, hipStream_t s) {
+  return dispatch_log2n<kPcMinLog2, DSP_MAX_LOG2N>(
+      log2n, [&](auto lg) { return launch_mac_n<decltype(lg)::value>(a, s); });
+}
 
 inline int64_t floor_div(int64_t a, int64_t b) {  // b > 0
   return a >= 0 ? a / b : -((-a + b - 1) / b);
@@ -308,12 +273,6 @@ size_t workspace_bytes(int64_t B, int log2n, int64_t slots) {
   return mul_sat((size_t)B, (size_t)slots, per);
 }
 
-// Whether [p, p + n) and [q, q + m) floats share a byte.
-bool pc_overlap(const float* p, int64_t n, const float* q, int64_t m) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return n > 0 && m > 0 && a < b + 4 * (uintptr_t)m && b < a + 4 * (uintptr_t)n;
-}
-
 int check_ring(int64_t B, int log2n, void* ws, size_t ws_bytes, int64_t slots, int64_t need,
                const float* twiddles) {
   DSP_REQUIRE(slots >= need, "slots=%lld < the %lld pairs this call touches", (long long)slots,
@@ -335,19 +294,10 @@ int partconv(const float* x, float* y, int64_t B, int64_t n_in, int64_t ld_x, in
   int64_t S = 0;
   if (int rc = pc_geometry(K, log2n, &S)) return rc;
   const int64_t N = int64_t(1) << log2n, H = N / 2, L = S * H + 3 * (N / 4);
-  DSP_REQUIRE(B >= 0 && n_in >= 0 && n_out >= 0, "negative count B=%lld n_in=%lld n_out=%lld",
-              (long long)B, (long long)n_in, (long long)n_out);
-  DSP_REQUIRE(offset >= 0 && offset <= K - 1, "offset=%lld outside [0, K - 1 = %d]",
-              (long long)offset, K - 1);
+  if (int rc = conv_check_io(x, y, B, n_in, ld_x, n_out, ld_y, offset, hist_in, hist_out, ld_hist,
+                             L, K))
+    return rc;
   DSP_REQUIRE(pos >= 0 && pos <= (int64_t(1) << 40), "pos=%lld outside [0, 2^40]", (long long)pos);
-  DSP_REQUIRE(n_in <= (int64_t(1) << 40), "n_in=%lld > 2^40", (long long)n_in);
-  DSP_REQUIRE(n_out <= n_in + (K - 1) - offset, "n_out=%lld > n_in + K - 1 - offset = %lld",
-              (long long)n_out, (long long)(n_in + (K - 1) - offset));
-  DSP_REQUIRE(ld_x >= n_in && ld_y >= n_out, "leading dimension too small (ld_x=%lld ld_y=%lld)",
-              (long long)ld_x, (long long)ld_y);
-  DSP_REQUIRE((!hist_in && !hist_out) || ld_hist >= L, "ld_hist=%lld < %lld", (long long)ld_hist,
-              (long long)L);
-  DSP_REQUIRE(hist_in != hist_out || !hist_in, "hist_in and hist_out are one buffer");
   DSP_REQUIRE(hist_in || pos == 0, "pos=%lld > 0 without hist_in", (long long)pos);
   DSP_REQUIRE(slots >= 1, "slots=%lld < 1", (long long)slots);
   // pairs: the stream's first; the first not complete before the call; the
@@ -367,11 +317,6 @@ int partconv(const float* x, float* y, int64_t B, int64_t n_in, int64_t ld_x, in
   const int64_t need = qf_hi >= lo ? qf_hi - lo + 1 : 0;
   if (B == 0) return DSP_OK;
   DSP_REQUIRE(taps && hf, "null pointer");
-  DSP_REQUIRE(x || n_in == 0, "null x");
-  DSP_REQUIRE(y || n_out == 0, "null y");
-  DSP_REQUIRE(B <= (int64_t(1) << 40) / (ld_x > ld_y ? (ld_x > 1 ? ld_x : 1) : (ld_y > 1 ? ld_y : 1)),
-              "batch too large");
-  DSP_REQUIRE(!pc_overlap(x, (B - 1) * ld_x + n_in, y, (B - 1) * ld_y + n_out), "x and y overlap");
   DSP_REQUIRE((reinterpret_cast<uintptr_t>(hf) & 7) == 0, "hf must be 8-byte aligned");
   if (int rc = check_ring(B, log2n, ws, ws_bytes, slots, need, twiddles)) return rc;
   PcArgs a{x, y, pos > 0 ? hist_in : nullptr, hist_out, taps,

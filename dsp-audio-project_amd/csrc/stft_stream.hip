@@ -138,23 +138,13 @@ int launch_stft_stream_n(const StspecArgs& a, hipStream_t s) {
                                  (unsigned)tg);
 }
 
+constexpr int kStspecMinLog2 = 5;
+
 int launch_stft_stream(const StspecArgs& a, int log2n, hipStream_t s) {
-  switch (log2n) {
-    case 5: return launch_stft_stream_n<5>(a, s);
-    case 6: return launch_stft_stream_n<6>(a, s);
-    case 7: return launch_stft_stream_n<7>(a, s);
-    case 8: return launch_stft_stream_n<8>(a, s);
-    case 9: return launch_stft_stream_n<9>(a, s);
-    case 10: return launch_stft_stream_n<10>(a, s);
-    case 11: return launch_stft_stream_n<11>(a, s);
-    case 12: return launch_stft_stream_n<12>(a, s);
-    case 13: return launch_stft_stream_n<13>(a, s);
-    case 14: return launch_stft_stream_n<14>(a, s);
-    default: return set_error(DSP_ENOTSUP, "log2n=%d outside [5, 14]", log2n);
-  }
+  return dispatch_log2n<kStspecMinLog2, DSP_MAX_LOG2N>(
+      log2n, [&](auto lg) { return launch_stft_stream_n<decltype(lg)::value>(a, s); });
 }
 
-constexpr int kStspecMinLog2 = 5;
 constexpr int64_t kStspecMaxBlock = int64_t(1) << 30;
 
 int64_t frames_complete(int64_t seen, int64_t N, int64_t hop) {

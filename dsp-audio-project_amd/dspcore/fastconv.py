@@ -34,7 +34,61 @@ def mode_geometry(mode: str, n: int, K: int) -> tuple[int, int]:
     raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
 
 
-class FastConv:
+class _ConvStream:
+    """What FastConv and PartConv share: the batch, the device and the output
+    buffer, the one-shot call and the push skeleton.  A subclass's __init__ sets
+    plan and K, calls _setup, builds _tables and _hist ([2, B, >= history
+    length], two buffers that swap roles), then calls reset(); it supplies
+    _oneshot(x, offset, n_out) and _run(block, n, hist_in, hist_out)."""
+
+    def _setup(self, batch, max_block, device) -> torch.device:
+        self.B = int(batch)
+        self.max_block = int(max_block)
+        if self.B < 1 or self.max_block < 1:
+            raise ValueError("batch and max_block must be >= 1")
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._ldy = max(4, -(-self.max_block // 4) * 4)
+        self._y = torch.empty((self.B, self._ldy), dtype=torch.float32, device=self.device)
+        return self.device
+
+    @property
+    def latency(self) -> float:
+        return (self.K - 1) / 2
+
+    def __call__(self, x: torch.Tensor, mode: str = "causal") -> torch.Tensor:
+        x = self._check(x, None)
+        if x.shape[1] < 1:
+            raise ValueError("a one-shot convolution needs at least one sample")
+        offset, n_out = mode_geometry(mode, int(x.shape[1]), self.K)
+        return self._oneshot(x, offset, n_out)
+
+    def reset(self) -> None:
+        """Back to the start of a stream: zero history (at position 0 nothing
+        else of the state is read)."""
+        self._hist[0].zero_()
+        self._cur = 0
+        self.samples = 0
+
+    def push(self, block: torch.Tensor) -> torch.Tensor:
+        block = self._check(block, self.max_block)
+        n = int(block.shape[1])
+        y = self._run(block, n, self._hist[self._cur], self._hist[1 - self._cur])
+        self._cur = 1 - self._cur
+        self.samples += n
+        return y
+
+    def _check(self, x, limit):
+        if (not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2
+                or x.shape[0] != self.B or (limit is not None and x.shape[1] > limit)):
+            what = f"{x.dtype} {tuple(x.shape)}" if torch.is_tensor(x) else type(x).__name__
+            lim = "n" if limit is None else f"n <= {limit}"
+            raise ValueError(f"expected float32 CUDA [{self.B}, {lim}], got {what}")
+        return ops._rows(x, "x")
+
+
+class FastConv(_ConvStream):
     """y = taps * x for `batch` float32 CUDA rows.
 
     __call__(x, mode) takes [batch, n >= 1] (any n) and returns a new tensor:
@@ -52,39 +106,18 @@ class FastConv:
         ops.require_gpu()
         self.plan = design.fastconv_plan(taps, log2n)
         self.K, self.n_fft, self.hop = self.plan.K, self.plan.n_fft, self.plan.hop
-        self.B = int(batch)
-        self.max_block = int(max_block)
-        if self.B < 1 or self.max_block < 1:
-            raise ValueError("batch and max_block must be >= 1")
-        self.device = torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        dev = self.device
+        dev = self._setup(batch, max_block, device)
         self._tables = ops.fastconv_tables(self.plan, dev)
         self._ldh = max(4, -(-(self.K - 1) // 4) * 4)   # every row starts 16-byte aligned
         self._hist = torch.zeros((2, self.B, self._ldh), dtype=torch.float32, device=dev)
-        self._ldy = max(4, -(-self.max_block // 4) * 4)
-        self._y = torch.empty((self.B, self._ldy), dtype=torch.float32, device=dev)
         self.reset()
 
-    @property
-    def latency(self) -> float:
-        return (self.K - 1) / 2
-
-    # -- one-shot ----------------------------------------------------------------
-    def __call__(self, x: torch.Tensor, mode: str = "causal") -> torch.Tensor:
-        x = self._check(x, None)
-        if x.shape[1] < 1:
-            raise ValueError("a one-shot convolution needs at least one sample")
-        offset, n_out = mode_geometry(mode, int(x.shape[1]), self.K)
+    def _oneshot(self, x, offset, n_out):
         return ops.fastconv(x, self.plan, offset, n_out, tables=self._tables)
 
-    # -- stream ------------------------------------------------------------------
-    def reset(self) -> None:
-        """Back to the start of a stream: zero history."""
-        self._hist[0].zero_()
-        self._cur = 0
-        self.samples = 0
+    def _run(self, block, n, hist_in, hist_out):
+        return ops.fastconv(block, self.plan, 0, n, hist_in, hist_out, out=self._y,
+                            tables=self._tables)
 
     def state_dict(self) -> dict:
         """The history and the sample count (host copies); a FastConv of the
@@ -100,23 +133,6 @@ class FastConv:
         self.reset()
         self._hist[0, :, :self.K - 1].copy_(hist)
         self.samples = int(sd["samples"])
-
-    def push(self, block: torch.Tensor) -> torch.Tensor:
-        block = self._check(block, self.max_block)
-        n = int(block.shape[1])
-        y = ops.fastconv(block, self.plan, 0, n, self._hist[self._cur], self._hist[1 - self._cur],
-                         out=self._y, tables=self._tables)
-        self._cur = 1 - self._cur
-        self.samples += n
-        return y
-
-    def _check(self, x, limit):
-        if (not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2
-                or x.shape[0] != self.B or (limit is not None and x.shape[1] > limit)):
-            what = f"{x.dtype} {tuple(x.shape)}" if torch.is_tensor(x) else type(x).__name__
-            lim = "n" if limit is None else f"n <= {limit}"
-            raise ValueError(f"expected float32 CUDA [{self.B}, {lim}], got {what}")
-        return ops._rows(x, "x")
 
 
 def convolve(x: torch.Tensor, taps, mode: str = "same") -> torch.Tensor:

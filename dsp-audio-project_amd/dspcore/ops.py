@@ -632,13 +632,46 @@ def stft_magnitude(x: torch.Tensor, n_fft: int, hop: int, frames: int,
     return out
 
 
-def fastconv_tables(plan, device: torch.device) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """(taps, hf, twiddles) of a design.FastConvPlan on `device`, cached."""
+def _conv_tables(plan, device: torch.device, hf_key: str):
+    """(taps, hf, twiddles) of a convolution plan on `device`, cached; hf_key
+    tells the two plans' spectra of the same taps apart."""
     taps = _cached(("fc_taps", plan.taps.tobytes(), device.index),
                    lambda: torch.from_numpy(plan.taps).to(device))
-    hf = _cached(("fc_hf", plan.log2n, plan.taps.tobytes(), device.index),
+    hf = _cached((hf_key, plan.log2n, plan.taps.tobytes(), device.index),
                  lambda: torch.from_numpy(np.ascontiguousarray(plan.hf).view(np.float32)).to(device))
     return taps, hf, _table("tw", plan.n_fft, device)
+
+
+def _conv_hist(h, name, B, need, device):
+    if h is not None and (h.dtype != torch.float32 or h.dim() != 2 or h.shape[0] != B
+                          or h.shape[1] < need or h.stride(1) != 1 or h.device != device):
+        raise ValueError(f"{name} must be float32 [{B}, >= {need}] on {device}")
+
+
+def _conv_prepare(x, n_out, out, hist_in, hist_out, need):
+    """The checked (x, B, n_in, n_out, out, hist) of a convolution call: float32
+    rows, a new `out` unless one is given, histories of >= need samples at one
+    pitch; hist is the one that carries that pitch (None without a history)."""
+    x = _rows(x, "x")
+    if x.dtype != torch.float32:
+        x = x.float()
+    B, n_in = x.shape
+    n_out = n_in if n_out is None else int(n_out)
+    if out is None:
+        out = torch.empty((B, n_out), dtype=torch.float32, device=x.device)
+    elif (out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B
+          or out.shape[1] < n_out or out.stride(1) != 1 or out.device != x.device):
+        raise ValueError(f"out must be float32 [{B}, >= {n_out}] on {x.device}")
+    _conv_hist(hist_in, "hist_in", B, need, x.device)
+    _conv_hist(hist_out, "hist_out", B, need, x.device)
+    if hist_in is not None and hist_out is not None and ld(hist_in) != ld(hist_out):
+        raise ValueError("hist_in and hist_out must have one row pitch")
+    return x, B, n_in, n_out, out, hist_in if hist_in is not None else hist_out
+
+
+def fastconv_tables(plan, device: torch.device) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(taps, hf, twiddles) of a design.FastConvPlan on `device`, cached."""
+    return _conv_tables(plan, device, "fc_hf")
 
 
 def fastconv(x: torch.Tensor, plan, offset: int = 0, n_out: int | None = None,
@@ -651,24 +684,7 @@ def fastconv(x: torch.Tensor, plan, offset: int = 0, n_out: int | None = None,
     last K - 1 samples of (history | row).  float32 CUDA [B, n] rows at any
     4-byte alignment.  tables: fastconv_tables(plan, device), for a caller that
     holds them."""
-    x = _rows(x, "x")
-    if x.dtype != torch.float32:
-        x = x.float()
-    B, n_in = x.shape
-    n_out = n_in if n_out is None else int(n_out)
-    if out is None:
-        out = torch.empty((B, n_out), dtype=torch.float32, device=x.device)
-    elif (out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B
-          or out.shape[1] < n_out or out.stride(1) != 1 or out.device != x.device):
-        raise ValueError(f"out must be float32 [{B}, >= {n_out}] on {x.device}")
-    for name, h in (("hist_in", hist_in), ("hist_out", hist_out)):
-        if h is not None and (h.dtype != torch.float32 or h.dim() != 2 or h.shape[0] != B
-                              or h.shape[1] < plan.K - 1 or h.stride(1) != 1
-                              or h.device != x.device):
-            raise ValueError(f"{name} must be float32 [{B}, >= {plan.K - 1}] on {x.device}")
-    if hist_in is not None and hist_out is not None and ld(hist_in) != ld(hist_out):
-        raise ValueError("hist_in and hist_out must have one row pitch")
-    hist = hist_in if hist_in is not None else hist_out
+    x, B, n_in, n_out, out, hist = _conv_prepare(x, n_out, out, hist_in, hist_out, plan.K - 1)
     taps, hf, tw = fastconv_tables(plan, x.device) if tables is None else tables
     lib = _lib.load()
     with torch.cuda.device(x.device):
@@ -683,11 +699,7 @@ def fastconv(x: torch.Tensor, plan, offset: int = 0, n_out: int | None = None,
 
 def partconv_tables(plan, device: torch.device) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(taps, hf, twiddles) of a design.PartConvPlan on `device`, cached."""
-    taps = _cached(("fc_taps", plan.taps.tobytes(), device.index),
-                   lambda: torch.from_numpy(plan.taps).to(device))
-    hf = _cached(("pc_hf", plan.log2n, plan.taps.tobytes(), device.index),
-                 lambda: torch.from_numpy(np.ascontiguousarray(plan.hf).view(np.float32)).to(device))
-    return taps, hf, _table("tw", plan.n_fft, device)
+    return _conv_tables(plan, device, "pc_hf")
 
 
 def partconv_slots(plan, n: int, offset: int = 0) -> int:
@@ -705,13 +717,6 @@ def partconv_workspace(plan, B: int, slots: int, device: torch.device) -> torch.
     return torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=device)
 
 
-def _partconv_hist(h, name, B, plan, device):
-    if h is not None and (h.dtype != torch.float32 or h.dim() != 2 or h.shape[0] != B
-                          or h.shape[1] < plan.hist_len or h.stride(1) != 1
-                          or h.device != device):
-        raise ValueError(f"{name} must be float32 [{B}, >= {plan.hist_len}] on {device}")
-
-
 def partconv(x: torch.Tensor, plan, offset: int = 0, n_out: int | None = None, pos: int = 0,
              hist_in: torch.Tensor | None = None, hist_out: torch.Tensor | None = None,
              ws: torch.Tensor | None = None, slots: int | None = None,
@@ -725,21 +730,7 @@ def partconv(x: torch.Tensor, plan, offset: int = 0, n_out: int | None = None, p
     partconv_slots), which a stream keeps between calls; without one the call
     allocates its own.  float32 CUDA [B, n] rows at any 4-byte alignment.
     tables: partconv_tables(plan, device), for a caller that holds them."""
-    x = _rows(x, "x")
-    if x.dtype != torch.float32:
-        x = x.float()
-    B, n_in = x.shape
-    n_out = n_in if n_out is None else int(n_out)
-    if out is None:
-        out = torch.empty((B, n_out), dtype=torch.float32, device=x.device)
-    elif (out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B
-          or out.shape[1] < n_out or out.stride(1) != 1 or out.device != x.device):
-        raise ValueError(f"out must be float32 [{B}, >= {n_out}] on {x.device}")
-    _partconv_hist(hist_in, "hist_in", B, plan, x.device)
-    _partconv_hist(hist_out, "hist_out", B, plan, x.device)
-    if hist_in is not None and hist_out is not None and ld(hist_in) != ld(hist_out):
-        raise ValueError("hist_in and hist_out must have one row pitch")
-    hist = hist_in if hist_in is not None else hist_out
+    x, B, n_in, n_out, out, hist = _conv_prepare(x, n_out, out, hist_in, hist_out, plan.hist_len)
     if ws is None:
         if pos:
             raise ValueError("a call at pos > 0 continues a stream and needs its ring (ws, slots)")
@@ -763,7 +754,7 @@ def partconv_prime(hist: torch.Tensor, plan, pos: int, ws: torch.Tensor, slots: 
     """Rebuilds a stream's ring at `pos` samples from hist [B, >= hist_len], the
     samples before pos (dsp_partconv_prime_f32)."""
     B = int(hist.shape[0])
-    _partconv_hist(hist, "hist", B, plan, hist.device)
+    _conv_hist(hist, "hist", B, plan.hist_len, hist.device)
     tw = _table("tw", plan.n_fft, hist.device)
     lib = _lib.load()
     with torch.cuda.device(hist.device):

@@ -21,12 +21,12 @@ from __future__ import annotations
 import torch
 
 from . import design, ops
-from .fastconv import MODES, mode_geometry
+from .fastconv import MODES, _ConvStream, mode_geometry
 
 __all__ = ["PartConv", "MODES", "mode_geometry"]
 
 
-class PartConv:
+class PartConv(_ConvStream):
     """y = taps * x for `batch` float32 CUDA rows.
 
     __call__(x, mode) takes [batch, n >= 1] (any n) and returns a new tensor:
@@ -44,42 +44,20 @@ class PartConv:
         ops.require_gpu()
         self.plan = design.partconv_plan(taps, log2n)
         self.K, self.n_fft, self.hop, self.S = self.plan.K, self.plan.n_fft, self.plan.P, self.plan.S
-        self.B = int(batch)
-        self.max_block = int(max_block)
-        if self.B < 1 or self.max_block < 1:
-            raise ValueError("batch and max_block must be >= 1")
-        self.device = torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        dev = self.device
+        dev = self._setup(batch, max_block, device)
         self._tables = ops.partconv_tables(self.plan, dev)
         self._L = self.plan.hist_len                    # a multiple of 4: rows stay 16-byte aligned
         self._hist = torch.zeros((2, self.B, self._L), dtype=torch.float32, device=dev)
         self.slots = ops.partconv_slots(self.plan, self.max_block)
         self._ws = ops.partconv_workspace(self.plan, self.B, self.slots, dev)
-        self._ldy = max(4, -(-self.max_block // 4) * 4)
-        self._y = torch.empty((self.B, self._ldy), dtype=torch.float32, device=dev)
         self.reset()
 
-    @property
-    def latency(self) -> float:
-        return (self.K - 1) / 2
-
-    # -- one-shot ----------------------------------------------------------------
-    def __call__(self, x: torch.Tensor, mode: str = "causal") -> torch.Tensor:
-        x = self._check(x, None)
-        if x.shape[1] < 1:
-            raise ValueError("a one-shot convolution needs at least one sample")
-        offset, n_out = mode_geometry(mode, int(x.shape[1]), self.K)
+    def _oneshot(self, x, offset, n_out):
         return ops.partconv(x, self.plan, offset, n_out, tables=self._tables)
 
-    # -- stream ------------------------------------------------------------------
-    def reset(self) -> None:
-        """Back to the start of a stream: zero history; at position 0 nothing
-        of the ring is read."""
-        self._hist[0].zero_()
-        self._cur = 0
-        self.samples = 0
+    def _run(self, block, n, hist_in, hist_out):
+        return ops.partconv(block, self.plan, 0, n, self.samples, hist_in, hist_out, self._ws,
+                            self.slots, out=self._y, tables=self._tables)
 
     def state_dict(self) -> dict:
         """The time-domain history and the sample count (host copies); a
@@ -98,22 +76,3 @@ class PartConv:
         self._hist[0].copy_(hist)
         self.samples = int(sd["samples"])
         ops.partconv_prime(self._hist[0], self.plan, self.samples, self._ws, self.slots)
-
-    def push(self, block: torch.Tensor) -> torch.Tensor:
-        block = self._check(block, self.max_block)
-        n = int(block.shape[1])
-        y = ops.partconv(block, self.plan, 0, n, self.samples, self._hist[self._cur],
-                         self._hist[1 - self._cur], self._ws, self.slots, out=self._y,
-                         tables=self._tables)
-        self._cur = 1 - self._cur
-        self.samples += n
-        return y
-
-    def _check(self, x, limit):
-        if (not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2
-                or x.shape[0] != self.B or (limit is not None and x.shape[1] > limit)):
-            what = f"{x.dtype} {tuple(x.shape)}" if torch.is_tensor(x) else type(x).__name__
-            lim = "n" if limit is None else f"n <= {limit}"
-            raise ValueError(f"expected float32 CUDA [{self.B}, {lim}], got {what}")
-        return ops._rows(x, "x")
-

@@ -8,10 +8,12 @@
 // oversized and odd chunk sizes, nonsense fmt/COMM fields, 80-bit rates at
 // their edges, random bytes), the playback header writer, and the chain
 // planners (tile tables, tile length, workspace sizes, x-state geometry,
-// Bluestein size) on edge-case geometries and cascades.  Every input buffer is
-// a heap copy of exactly its length, so any read past it is an ASan report.
-// Invariants of successful parses are checked; exit status 0 means no
-// sanitizer report and no broken invariant.
+// Bluestein size) on edge-case geometries and cascades, and the two fast
+// convolutions' geometry functions and argument checks (every malformed call
+// is rejected before a launch; the pointers are dummies that no check
+// dereferences).  Every input buffer is a heap copy of exactly its length, so
+// any read past it is an ASan report.  Invariants of successful parses are
+// checked; exit status 0 means no sanitizer report and no broken invariant.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -21,6 +23,8 @@
 #include <vector>
 
 #include "dspcore.h"
+#include "dspcore_fastconv.h"
+#include "dspcore_partconv.h"
 
 namespace {
 
@@ -311,6 +315,213 @@ void planners() {
   CHECK(dsp_chain_path(5) == DSP_EINVAL, "chain path 5");
 }
 
+// dsp_fastconv_f32 / dsp_partconv_f32 / dsp_partconv_prime_f32 arguments; the
+// defaults are a valid call (N = 64; K = 17 or 40 taps; 3 rows of 100).
+float* fake(uintptr_t v) { return reinterpret_cast<float*>(v); }
+
+constexpr int32_t kDefaultK = std::numeric_limits<int32_t>::min();
+
+struct ConvCall {
+  float* x = fake(0x10000);
+  float* y = fake(0x80000);
+  int64_t B = 3, n_in = 100, ld_x = 100, n_out = 100, ld_y = 100, offset = 0, pos = 0;
+  float* hist_in = fake(0x100000);
+  float* hist_out = fake(0x180000);
+  int64_t ld_hist = -1;  // -1: the history length
+  float* taps = fake(0x200000);
+  int32_t K = kDefaultK;  // kDefaultK: 17 (fastconv), 40 (partconv)
+  float* hf = fake(0x280000);
+  int32_t log2n = 6;
+  void* ws = fake(0x400000);
+  int64_t ws_bytes = -1;  // -1: what B rows of `slots` need at N = 64
+  int64_t slots = 7;
+  float* tw = fake(0x300000);
+  size_t ring_bytes() const {
+    return ws_bytes >= 0 ? (size_t)ws_bytes
+                         : (size_t)(B > 0 ? B : 0) * (size_t)(slots > 0 ? slots : 0) * (512 + 4);
+  }
+  int fast() const {
+    const int32_t k = K == kDefaultK ? 17 : K;
+    return dsp_fastconv_f32(x, y, B, n_in, ld_x, n_out, ld_y, offset, hist_in, hist_out,
+                            ld_hist >= 0 ? ld_hist : (k > 1 ? k - 1 : 0), taps, k, hf, log2n, tw,
+                            nullptr);
+  }
+  int part() const {
+    return dsp_partconv_f32(x, y, B, n_in, ld_x, n_out, ld_y, offset, pos, hist_in, hist_out,
+                            ld_hist >= 0 ? ld_hist : 112, taps, K == kDefaultK ? 40 : K, hf, log2n, ws,
+                            ring_bytes(), slots, tw, nullptr);
+  }
+  int prime() const {
+    return dsp_partconv_prime_f32(hist_in, B, ld_hist >= 0 ? ld_hist : 112, pos,
+                                  K == kDefaultK ? 40 : K, log2n, ws, ring_bytes(), slots, tw,
+                                  nullptr);
+  }
+};
+
+void rejected(int rc, int want, const char* what, int i) {
+  CHECK(rc == want, "%s case %d: rc %d, expected %d", what, i, rc, want);
+  CHECK(std::strlen(dsp_last_error()) > 0, "%s case %d: empty error string", what, i);
+}
+
+void conv_arguments() {
+  constexpr int64_t kMax = std::numeric_limits<int64_t>::max();
+  constexpr int32_t kMax32 = std::numeric_limits<int32_t>::max();
+  // the geometry functions: a status or a value, never a trap
+  for (int32_t K : {-1, 0, 1, 2, 17, 40, 8193, 8194, 1 << 20, (1 << 20) + 1, kMax32}) {
+    const int lf = dsp_fastconv_log2n(K), lp = dsp_partconv_log2n(K);
+    CHECK(lf == DSP_EINVAL || lf == DSP_ENOTSUP || (lf >= 6 && lf <= 14), "fastconv log2n %d", lf);
+    CHECK(lp == DSP_EINVAL || (lp >= 6 && lp <= 14), "partconv log2n %d", lp);
+    CHECK((K >= 1 && K <= 8193) == (lf >= 6), "fastconv log2n %d for K=%d", lf, K);
+    CHECK((K >= 1 && K <= (1 << 20)) == (lp >= 6), "partconv log2n %d for K=%d", lp, K);
+    for (int32_t lg : {-1, 0, 5, 6, 10, 14, 15, 31, 64, kMax32}) {
+      const int64_t L = dsp_partconv_hist_len(K, lg);
+      CHECK(L == DSP_EINVAL || L == DSP_ENOTSUP || L >= K - 1, "hist_len %lld", (long long)L);
+      for (int64_t n : {(int64_t)-1, (int64_t)0, (int64_t)100, (int64_t)1 << 41,
+                        ((int64_t)1 << 41) + 1, kMax})
+        for (int64_t off : {(int64_t)-1, (int64_t)0, (int64_t)K - 1, (int64_t)K, kMax}) {
+          const int64_t sl = dsp_partconv_slots(K, lg, n, off);
+          CHECK(sl == DSP_EINVAL || sl == DSP_ENOTSUP || sl >= 2, "slots %lld", (long long)sl);
+          CHECK((L < 0) <= (sl < 0), "slots %lld where hist_len is %lld", (long long)sl,
+                (long long)L);
+        }
+    }
+  }
+  CHECK(dsp_partconv_hist_len(40, 6) == 112 && dsp_partconv_slots(40, 6, 100, 0) == 7, "N = 64");
+  for (int64_t B : {(int64_t)-1, (int64_t)0, (int64_t)3, (int64_t)1 << 40, kMax})
+    for (int32_t lg : {-1, 5, 6, 14, 15, 64})
+      for (int64_t slots : {(int64_t)-1, (int64_t)0, (int64_t)7, (int64_t)1 << 30, kMax}) {
+        const size_t w = dsp_partconv_workspace_bytes(B, lg, slots);
+        const bool ok = B >= 0 && slots >= 0 && lg >= 6 && lg <= 14;
+        CHECK(ok || (w == 0 && std::strlen(dsp_last_error()) > 0), "workspace %zu", w);
+        if (ok && B == 3 && slots == 7) CHECK(w == 21 * ((size_t(8) << lg) + 4), "workspace %zu", w);
+        if (ok && B == kMax && slots == kMax) CHECK(w == SIZE_MAX, "workspace wraps: %zu", w);
+      }
+  // dsp_fastconv_f32: tests/test_fastconv_plan.py's malformed calls, and absurd sizes
+  auto with = [](auto set) {
+    ConvCall c;
+    set(c);
+    return c;
+  };
+  const auto all_null = [](ConvCall& c) {
+    c.x = c.y = c.hist_in = c.hist_out = c.taps = c.hf = c.tw = nullptr;
+    c.ws = nullptr;
+  };
+  const ConvCall fast_einval[] = {
+      with([](ConvCall& c) { c.K = 0; }), with([](ConvCall& c) { c.K = -1; }),
+      with([](ConvCall& c) { c.K = 34; }),
+      with([](ConvCall& c) { c.B = -1; }), with([](ConvCall& c) { c.n_in = -1; }),
+      with([](ConvCall& c) { c.n_out = -1; }), with([](ConvCall& c) { c.offset = -1; }),
+      with([](ConvCall& c) { c.offset = 17; }), with([](ConvCall& c) { c.n_out = c.ld_y = 117; }),
+      with([](ConvCall& c) { c.n_out = c.ld_y = 114, c.offset = 3; }),
+      with([](ConvCall& c) { c.ld_x = 99; }), with([](ConvCall& c) { c.ld_y = 99; }),
+      with([](ConvCall& c) { c.ld_hist = 15; }),
+      with([](ConvCall& c) { c.ld_hist = 15, c.hist_in = nullptr; }),
+      with([](ConvCall& c) { c.ld_hist = 15, c.hist_out = nullptr; }),
+      with([](ConvCall& c) { c.hist_out = c.hist_in; }), with([](ConvCall& c) { c.x = nullptr; }),
+      with([](ConvCall& c) { c.y = nullptr; }), with([](ConvCall& c) { c.taps = nullptr; }),
+      with([](ConvCall& c) { c.hf = nullptr; }), with([](ConvCall& c) { c.tw = nullptr; }),
+      with([](ConvCall& c) { c.y = fake(0x10000 + 4 * 50); }),
+      with([](ConvCall& c) { c.hf = fake(0x280004); }),
+      with([](ConvCall& c) { c.B = kMax; }), with([](ConvCall& c) { c.B = (int64_t)1 << 40; }),
+      with([](ConvCall& c) { c.n_in = c.ld_x = kMax; }),
+      with([](ConvCall& c) { c.n_out = c.ld_y = kMax; }),
+      with([](ConvCall& c) { c.ld_x = c.ld_y = kMax; }),
+      with([](ConvCall& c) { c.n_in = c.n_out = c.ld_x = c.ld_y = ((int64_t)1 << 40) + 1; }),
+      with([](ConvCall& c) { c.offset = kMax; }),
+      with([](ConvCall& c) { c.B = c.n_in = c.n_out = c.ld_x = c.ld_y = c.ld_hist = kMax; })};
+  int i = 0;
+  for (const ConvCall& c : fast_einval) rejected(c.fast(), DSP_EINVAL, "fastconv", i++);
+  for (int32_t lg : {5, 15, 0, -1, 31, kMax32}) {
+    rejected(with([&](ConvCall& c) { c.log2n = lg; }).fast(), DSP_ENOTSUP, "fastconv log2n", lg);
+    // ... also with every pointer null, and whatever else is wrong
+    rejected(with([&](ConvCall& c) { all_null(c), c.log2n = lg, c.K = 0; }).fast(), DSP_ENOTSUP,
+             "fastconv log2n", lg);
+    rejected(with([&](ConvCall& c) { c.log2n = lg, c.B = kMax, c.K = -1; }).fast(), DSP_ENOTSUP,
+             "fastconv log2n", lg);
+  }
+  // (B == 0 passes every check and launches nothing)
+  CHECK(with([](ConvCall& c) { c.B = 0; }).fast() == DSP_OK, "fastconv B = 0");
+  CHECK(with([&](ConvCall& c) { all_null(c), c.B = 0; }).fast() == DSP_OK,
+        "fastconv B = 0, null pointers");
+  rejected(with([](ConvCall& c) { c.B = 0, c.K = 0; }).fast(), DSP_EINVAL, "fastconv B = 0", 0);
+  rejected(with([](ConvCall& c) { c.B = 0, c.offset = 17; }).fast(), DSP_EINVAL, "fastconv B = 0", 1);
+  // dsp_partconv_f32: tests/test_partconv_plan.py's
+  const ConvCall part_einval[] = {
+      with([](ConvCall& c) { c.K = 0; }), with([](ConvCall& c) { c.K = -1; }),
+      with([](ConvCall& c) { c.K = (1 << 20) + 1; }),
+      with([](ConvCall& c) { c.K = 32 * 1024 + 1, c.ld_hist = 1 << 21; }),
+      with([](ConvCall& c) { c.B = -1; }), with([](ConvCall& c) { c.n_in = -1; }),
+      with([](ConvCall& c) { c.n_out = -1; }), with([](ConvCall& c) { c.offset = -1; }),
+      with([](ConvCall& c) { c.offset = 40; }), with([](ConvCall& c) { c.pos = -1; }),
+      with([](ConvCall& c) { c.pos = ((int64_t)1 << 40) + 1; }),
+      with([](ConvCall& c) { c.n_out = c.ld_y = 140; }),
+      with([](ConvCall& c) { c.n_out = c.ld_y = 137, c.offset = 3; }),
+      with([](ConvCall& c) { c.ld_x = 99; }), with([](ConvCall& c) { c.ld_y = 99; }),
+      with([](ConvCall& c) { c.ld_hist = 111; }),
+      with([](ConvCall& c) { c.ld_hist = 111, c.hist_in = nullptr; }),
+      with([](ConvCall& c) { c.ld_hist = 111, c.hist_out = nullptr; }),
+      with([](ConvCall& c) { c.hist_out = c.hist_in; }),
+      with([](ConvCall& c) { c.pos = 64, c.hist_in = nullptr; }),
+      with([](ConvCall& c) { c.slots = 0; }), with([](ConvCall& c) { c.slots = -1; }),
+      with([](ConvCall& c) { c.slots = 3; }), with([](ConvCall& c) { c.pos = 64, c.slots = 4; }),
+      with([](ConvCall& c) { c.ws_bytes = 3 * 7 * (512 + 4) - 1; }),
+      with([](ConvCall& c) { c.ws = fake(0x400008); }), with([](ConvCall& c) { c.hf = fake(0x280004); }),
+      with([](ConvCall& c) { c.tw = fake(0x300004); }), with([](ConvCall& c) { c.x = nullptr; }),
+      with([](ConvCall& c) { c.y = nullptr; }), with([](ConvCall& c) { c.taps = nullptr; }),
+      with([](ConvCall& c) { c.hf = nullptr; }), with([](ConvCall& c) { c.tw = nullptr; }),
+      with([](ConvCall& c) { c.ws = nullptr; }),
+      with([](ConvCall& c) { c.y = fake(0x10000 + 4 * 50); }),
+      with([](ConvCall& c) { c.B = kMax; }), with([](ConvCall& c) { c.B = (int64_t)1 << 40; }),
+      with([](ConvCall& c) { c.n_in = c.ld_x = kMax; }),
+      with([](ConvCall& c) { c.n_out = c.ld_y = kMax; }),
+      with([](ConvCall& c) { c.ld_x = c.ld_y = kMax; }), with([](ConvCall& c) { c.pos = kMax; }),
+      with([](ConvCall& c) { c.slots = kMax, c.ws_bytes = kMax; }),
+      with([](ConvCall& c) { c.offset = kMax; }),
+      with([](ConvCall& c) {
+        c.B = c.n_in = c.n_out = c.ld_x = c.ld_y = c.ld_hist = c.slots = c.ws_bytes = kMax;
+      })};
+  i = 0;
+  for (const ConvCall& c : part_einval) rejected(c.part(), DSP_EINVAL, "partconv", i++);
+  for (int32_t lg : {5, 15, 0, -1, 31, kMax32}) {
+    rejected(with([&](ConvCall& c) { c.log2n = lg; }).part(), DSP_ENOTSUP, "partconv log2n", lg);
+    rejected(with([&](ConvCall& c) { all_null(c), c.log2n = lg, c.K = 0; }).part(), DSP_ENOTSUP,
+             "partconv log2n", lg);
+    rejected(with([&](ConvCall& c) { c.log2n = lg, c.B = kMax, c.K = -1; }).part(), DSP_ENOTSUP,
+             "partconv log2n", lg);
+    rejected(with([&](ConvCall& c) { c.log2n = lg, c.pos = 100, c.hist_in = nullptr; }).prime(),
+             DSP_ENOTSUP, "prime log2n", lg);
+  }
+  CHECK(with([](ConvCall& c) { c.B = 0; }).part() == DSP_OK, "partconv B = 0");
+  CHECK(with([&](ConvCall& c) { all_null(c), c.B = 0; }).part() == DSP_OK,
+        "partconv B = 0, null pointers");
+  rejected(with([](ConvCall& c) { c.B = 0, c.K = 0; }).part(), DSP_EINVAL, "partconv B = 0", 0);
+  rejected(with([](ConvCall& c) { c.B = 0, c.offset = 40; }).part(), DSP_EINVAL, "partconv B = 0", 1);
+  rejected(with([](ConvCall& c) { c.B = 0, c.pos = 5, c.hist_in = nullptr; }).part(), DSP_EINVAL,
+           "partconv B = 0", 2);
+  // dsp_partconv_prime_f32 (at pos = 100: one pair to transform)
+  const ConvCall prime_einval[] = {
+      with([](ConvCall& c) { c.K = 0; }), with([](ConvCall& c) { c.K = -1; }),
+      with([](ConvCall& c) { c.B = -1; }),
+      with([](ConvCall& c) { c.pos = -1; }), with([](ConvCall& c) { c.ld_hist = 111; }),
+      with([](ConvCall& c) { c.slots = 0; }), with([](ConvCall& c) { c.hist_in = nullptr; }),
+      with([](ConvCall& c) { c.ws = nullptr; }), with([](ConvCall& c) { c.tw = nullptr; }),
+      with([](ConvCall& c) { c.ws = fake(0x400004); }), with([](ConvCall& c) { c.ws_bytes = 100; }),
+      with([](ConvCall& c) { c.K = 320, c.ld_hist = 1 << 12, c.pos = 1 << 12, c.slots = 8; }),
+      with([](ConvCall& c) { c.B = kMax; }), with([](ConvCall& c) { c.ld_hist = kMax; }),
+      with([](ConvCall& c) { c.slots = kMax, c.ws_bytes = kMax; }),
+      with([](ConvCall& c) { c.pos = kMax; })};
+  i = 0;
+  for (ConvCall c : prime_einval) {
+    if (c.pos == 0) c.pos = 100;
+    rejected(c.prime(), DSP_EINVAL, "prime", i++);
+  }
+  CHECK(with([](ConvCall& c) { c.B = 0, c.pos = 100; }).prime() == DSP_OK, "prime B = 0");
+  CHECK(with([&](ConvCall& c) { all_null(c), c.B = 0, c.pos = 100; }).prime() == DSP_OK,
+        "prime B = 0, null pointers");
+  rejected(with([](ConvCall& c) { c.B = 0, c.pos = 100, c.K = 0; }).prime(), DSP_EINVAL,
+           "prime B = 0", 0);
+}
+
 }  // namespace
 
 void aiff_corpus() {
@@ -358,6 +569,7 @@ int main() {
   aiff_corpus();
   header_writer();
   planners();
+  conv_arguments();
   std::printf("host_fuzz: %ld parsed, %ld rejected, %d failures\n", g_parsed, g_rejected, g_fail);
   return g_fail ? 1 : 0;
 }

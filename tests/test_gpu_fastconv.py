@@ -26,37 +26,13 @@ import pytest
 import torch
 
 import fastconv_model as fm
+from conv_gpu_helpers import SENT, YSENT, _bits, _design, _direct, _ops, _tail
 
 pytestmark = pytest.mark.gpu
-
-SENT = 1.0e3
-YSENT = np.array([0xCAFEF00D], dtype=np.uint32).view(np.int32)[0].item()
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _design():
-    from dspcore import design
-    return design
-
-
-def _ops():
-    from dspcore import ops
-    return ops
 
 
 def _plan(taps, N):
     return _design().fastconv_plan(taps, log2n=N.bit_length() - 1)
-
-
-def _tail(hist, x, k1):
-    """The last k1 samples of (hist | x) per row (device tensors)."""
-    if hist is None:
-        hist = torch.zeros((x.shape[0], k1), dtype=x.dtype, device=x.device)
-    cat = torch.cat([hist, x], dim=1)
-    return cat[:, cat.shape[1] - k1:]
 
 
 def _call(gpu, x, plan, offset=0, n_out=None, hist=None, odd=1, lead=0, tag=""):
@@ -89,14 +65,6 @@ def _call(gpu, x, plan, offset=0, n_out=None, hist=None, odd=1, lead=0, tag=""):
     if hist is not None:
         assert torch.equal(_bits(hin[:, :k1]), _bits(hist)) and bool((hin[:, k1:] == SENT).all())
     return yb[:, :n_out].view(torch.float32).clone(), hout[:, :k1].clone()
-
-
-def _direct(x, taps, offset, n_out):
-    """The direct kernel on the same rows: y [B, n_out]."""
-    design = _design()
-    n = int(x.shape[1])
-    src = design.SrcPlan(1, 1, int(taps.size), np.asarray(taps, np.float64), offset, n, n_out, 0)
-    return _ops().src_polyphase(x.contiguous(), src)
 
 
 # --------------------------------------------------------------------------- values

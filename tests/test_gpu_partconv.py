@@ -29,25 +29,9 @@ import pytest
 import torch
 
 import partconv_model as pm
+from conv_gpu_helpers import SENT, YSENT, _bits, _design, _ops, _tail
 
 pytestmark = pytest.mark.gpu
-
-SENT = 1.0e3
-YSENT = np.array([0xCAFEF00D], dtype=np.uint32).view(np.int32)[0].item()
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _design():
-    from dspcore import design
-    return design
-
-
-def _ops():
-    from dspcore import ops
-    return ops
 
 
 def _plan(taps, N):
@@ -62,14 +46,6 @@ class _Ring:
         self.slots = slots
         self.ws = _ops().partconv_workspace(plan, B, slots, gpu)
         self.ws.view(torch.float32).fill_(SENT)
-
-
-def _tail(hist, x, L):
-    """The last L samples of (hist | x) per row (device tensors)."""
-    if hist is None:
-        hist = torch.zeros((x.shape[0], L), dtype=x.dtype, device=x.device)
-    cat = torch.cat([hist, x], dim=1)
-    return cat[:, cat.shape[1] - L:]
 
 
 def _call(gpu, x, plan, offset=0, n_out=None, pos=0, hist=None, ring=None, odd=1, lead=0, tag=""):
