@@ -146,16 +146,19 @@ __host__ __device__ __forceinline__ float flush_tap(float t, float thr) {
 // otherwise -- and fin = the kernels' canonical sum of the finite samples with
 // the flushed taps: two FMA chains over x ascending, term t in chain
 // (pb - t) & 1, fin = chain 0 + chain 1 (pb = q for the packed kernels, whose
-// chains follow x's absolute parity; pb = T - 1 for the generic ones, whose
-// chains follow the parity from the window start q - (T - 1)); pb < 0: one
-// chain (the odd-M register-blocked kernel).  xat(t) returns x[q - t].
+// chains follow x's absolute parity; pb = T - 1 for the generic ones and the
+// odd-M register-blocked kernel, whose chains follow the parity from the
+// window start q - (T - 1)).  No caller passes pb < 0 (one chain, fin = c0).
+// xat(t) returns x[q - t].
 template <class XAT>
 __device__ __forceinline__ void window_sums(const float* __restrict__ taps, int K, int L, int phi,
                                             float thr, int pb, XAT xat, float& nf, float& fin) {
   float sn = 0.f, c0 = 0.f, c1 = 0.f;
   // (the tap index in a VGPR even where it is wave-uniform: the rare path runs
   // inside kernels whose SGPRs are all taken)
-  int t = (K - 1 - phi) / L;
+  // (a phase at or past K has no tap -- K < L -- and the division would round
+  // its negative numerator up to t = 0)
+  int t = phi < K ? (K - 1 - phi) / L : -1;
   asm volatile("" : "+v"(t));
 #pragma unroll 1
   for (; t >= 0; --t) {

@@ -240,14 +240,23 @@ __global__ __launch_bounds__(kGenNT) void k_src_generic(
   const int64_t qhi = ((m1 - 1) * M + c) / L;
   const int64_t qa = qlo & ~(int64_t)3;
   __shared__ float s_red[kGenNT / 64];
+  __shared__ int s_nf[kGenNT / 64];
   const bool nf = load_window<kGenNT>(s_win, xr, qa, (int)(qhi - qa + 1), n_in, vec_x != 0);
+  // One flag per wave and the barrier below, not __syncthreads_or: that keeps
+  // 256 bytes of static LDS of its own, and launch_src_rows leaves this kernel
+  // 64 beside a bank and window of kLdsMax bytes.
+  if ((tid & (kWave - 1)) == 0) s_nf[tid / kWave] = 0;
+  if (nf) s_nf[tid / kWave] = 1;
   const float thr = block_flush_threshold<kGenNT>(taps, K, L, s_red);
   for (int i = tid; i < L * T; i += kGenNT) {
     const int phi = i / T, u = i - phi * T;
     const int k = phi + L * (T - 1 - u);
     s_bank[i] = (k < K) ? flush_tap(taps[k], thr) : 0.f;
   }
-  const bool any_nf = __syncthreads_or(nf);
+  __syncthreads();
+  bool any_nf = false;
+#pragma unroll
+  for (int w = 0; w < kGenNT / kWave; ++w) any_nf |= s_nf[w] != 0;
 
   // Output stores are coalesced directly (consecutive threads, consecutive m).
   // (q, phi) of j = m*M + c advance by a fixed (dq, dphi) per iteration, so the
@@ -331,7 +340,7 @@ int launch_src_rows(const float* x, float* y, int64_t B, int64_t n_in, int64_t l
     const int64_t w = ((int64_t)(t - 1) * M) / L + T + 2 + 8;
     return (int64_t)(bank_floats + ((w + 3) / 4) * 4) * 4;
   };
-  constexpr int64_t kLdsMax = 160 * 1024 - 64;  // (the kernel's static LDS: s_red)
+  constexpr int64_t kLdsMax = 160 * 1024 - 64;  // (the kernel's static LDS: s_red, s_nf)
   while (tile > 64 && lds_bytes(tile) > kLdsMax) tile >>= 1;
   if (lds_bytes(tile) > kLdsMax)
     return set_error(DSP_ENOTSUP, "tap bank L*ceil(K/L)=%d floats does not fit in LDS", L * T);

@@ -12,8 +12,9 @@ and a NaN anywhere in the spectrum's segment makes every bin NaN (:92-93).
 
 Rows of each config carry NaN, +inf and -inf at a delay output's window edge
 (L3/M2: the branch whose only flushed-free tap is the centre), off its centre,
-at tile and sub-chunk boundaries of the single-pass kernels and of the SRC
-kernel's blocks, and at a channel's first and last samples.  Every path --
+at tile and sub-chunk boundaries of the single-pass kernels (the standalone
+SRC kernels' own block boundaries are tests/test_gpu_src_edges.py's), and at a
+channel's first and last samples.  Every path --
 the drop-in module, Chain.run's single-pass kernel and its two-launch chain
 (dsp_chain_path(1)), and the host-resident HostChain -- must give the oracle's
 (oracle/dsp_ref_cpu.py) non-finite masks exactly: y's NaN / +inf / -inf, z's
